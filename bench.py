@@ -13,6 +13,10 @@ Workloads (--config, numbered like BASELINE.json's list; 3 is the one the metric
 A "step" = one outer simulation step (World.step(fixed_dt=True)) of the whole batch, forward, plus its share of the
 backward sweep of sum |pos_T|^2; the timed region is K forward steps followed by the full reverse sweep through them.
 Prints ONE JSON line on rank 0.
+  --full              also measures what the headline does not need: the CPU baseline (configs 2 and 3).  A plain run sets up,
+                      warms up, times the K steps and prints the line.
+  --dump-outputs DIR  after the timed region, writes what it computed (final state and gradients, float64) as DIR/<name>.npy;
+                      the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -62,6 +66,22 @@ def detect_algorithmic_bytes(E):
     active = st[:, :, 0] > 0
     per_pair = nch * 48 + st[:, :, 0] * 256 * 32 + st[:, :, 1] * 84 + cnt * 112 + 2 * 20 * 8
     return float((per_pair * active).sum())
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """arrays: (name, array or tensor) pairs -> path/<name>.npy in float64.  Past DUMP_BYTES in all, every array keeps the same fixed,
+    seeded sample of its rows (leading axis), so the files stay comparable between runs and builds."""
+    os.makedirs(path, exist_ok=True)
+    arrays = [(n, np.ascontiguousarray(np.asarray(a.detach().cpu() if hasattr(a, "detach") else a, dtype=np.float64))) for n, a in arrays]
+    total = sum(a.nbytes for _, a in arrays)
+    for n, a in arrays:
+        if total > DUMP_BYTES and a.ndim > 0 and a.shape[0] > 1:
+            m = max(1, int(a.shape[0] * DUMP_BYTES / total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], m, replace=False))]
+        np.save(os.path.join(path, n + ".npy"), a)
 
 
 def lib_hash():
@@ -245,6 +265,8 @@ def bench_config1(args):
     w, g = run()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("p", w.get_p()), ("v", w.v), ("d_loss_d_rad", np.array([g]))])
     print(json.dumps({
         "metric": "sim steps/sec (fwd+bwd), BASELINE configs[0]", "value": K / dt, "unit": "steps/s", "n_gpus": 1, "steps": K, "warmup": Wm,
         "ms_per_step": 1e3 * dt / K, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -298,12 +320,12 @@ def bench_config5(args, dist, rank, world, dev, cdev, backend):
             tr = sharding.gather_scenes(tr.to(cdev), nsc * world, dist)
         torch.cuda.synchronize(); t["total_s"] = time.perf_counter() - t0
         ev, meshsdf.GRID_EVENTS = meshsdf.GRID_EVENTS, None
-        return t, ev, lat.grad, [m[1] if isinstance(m[1], int) else len(m[1]) for m in w.meshes]
+        return t, ev, lat.grad, [m[1] if isinstance(m[1], int) else len(m[1]) for m in w.meshes], tr
     for _ in range(max(1, min(args.warmup, 1))):
         iteration(min(B, 8), False)                  # warm-up: the same chain on eight scenes (kernels loaded, allocator primed)
     if dist is not None:
         dist.barrier()
-    t, ev, grad, nfaces = iteration(B, True)
+    t, ev, grad, nfaces, tr = iteration(B, True)
     tot = t["total_s"]
     if dist is not None:
         tt = torch.tensor([tot], device=cdev, dtype=torch.float64)
@@ -311,6 +333,8 @@ def bench_config5(args, dist, rank, world, dev, cdev, backend):
         tot = float(tt.item())
     if rank != 0:
         return
+    if args.dump_outputs:       # trajectories of every scene (gathered), the latent gradient of this rank's scenes
+        dump_outputs(args.dump_outputs, [("trajectory", tr.reshape(-1, K, 13)), ("latent_grad", grad)])
     ms = np.array([a.elapsed_time(b) for a, b, _n in ev])
     pts = float(sum(n for _a, _b, n in ev))
     flops = 2.0 * IGR_MAC_PER_POINT * pts
@@ -348,7 +372,10 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=32, help="scenes of the batch the CPU baseline steps (at least one per core)")
     ap.add_argument("--cpu-steps", type=int, default=3, help="steps per sampled scene in the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=16, help="host threads of the CPU baseline (capped by the affinity mask)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need (the CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--lockstep", action="store_true", help="one BatchEngine.step() per outer step for the whole batch (every scene waits for the slowest of each step) instead of BatchEngine.run(K)")
     ap.add_argument("--push", type=float, default=0.0, help="random lateral start velocity (0 = BASELINE config 3 as specified)")
     ap.add_argument("--spin-only", action="store_true", help="config 5: time only the 200-step spin of given inertias (round 2's line), "
@@ -532,7 +559,7 @@ def main():
     # (rejected attempts left nothing on the tape)
     n_sweeps = int((E.arr["nsub"] - lo).max().item())
     E.backward_sweep(n_sweeps)
-    gather_results()
+    final = gather_results()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -545,6 +572,10 @@ def main():
 
     if rank != 0:
         return
+    if args.dump_outputs:       # the gathered result of the timed region: final poses and per-scene gradients of every scene
+        cols = [("pose", E.arr["pose"]), ("g_prm", E.adj["g_prm"]), ("g_mass", E.adj["g_mass"]), ("g_fric", E.adj["g_fric"])]
+        parts = torch.split(final, [a[0].numel() for _, a in cols], dim=1)
+        dump_outputs(args.dump_outputs, [(n, p.reshape((-1,) + tuple(a.shape[1:]))) for (n, a), p in zip(cols, parts)])
     lcp_ms = np.array([a.elapsed_time(b) for a, b, c, d in ev])
     det_ms = np.array([c.elapsed_time(d) for a, b, c, d in ev])
     nc = E.get("nc")
@@ -638,7 +669,7 @@ def main():
     res.update(extra)
     if pmc_note:
         res["config"]["pmc_note"] = pmc_note
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         # host cores: this process's share of the box (a one-GPU box is given 16 cores' worth, whatever the affinity mask says)
         threads = max(1, min(args.cpu_threads, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)))
         if cfg in (2, 3):

@@ -6,7 +6,7 @@
 # Usage: tools/collect_profiles.sh <part>
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p profiles
-bench() { timeout -k 10 900 python3 bench.py --config $1 > gpurun_out/r3_bench_config$1.json 2> gpurun_out/r3_bench_config$1.err || echo "config $1 failed"; cut -c1-260 gpurun_out/r3_bench_config$1.json; }
+bench() { timeout -k 10 900 python3 bench.py --full --config $1 > profiles/r3_bench_config$1.json 2> $TMPDIR/r3_bench_config$1.err || echo "config $1 failed"; cut -c1-260 profiles/r3_bench_config$1.json; }
 kstats() {   # config, steps, extra args
     local c=$1 s=$2; shift 2
     rm -rf gpurun_out/ks$c
