@@ -18,16 +18,17 @@
 // with a 3x3 matrix C_c per contact.  The two are the same Newton system, so the iterates agree
 // with the reference to rounding (verified against its goldens: 1e-13 on the velocities).
 //
-// Mapping: blockDim = 64 (one wave) per scene.  LDS: H = Q + sum P C P^T (odd leading dimension => conflict free
-// column walks), contact points, per-contact 3-vectors / C matrices, nz-sized vectors.  The compiled system sizes
-// (n = 54: 8 bodies + 6 equality rows; n = 18) are factored with one matrix row per lane in registers (kkt_reg.h);
-// a body pinned by identity equality rows is eliminated in closed form first.  With maxc <= 128 the per-contact IPM
-// state (s, z, rz, ds, dz, d: NR doubles each) of two contacts per lane lives in registers
-// (lcp_contact_forward_reg_kernel); beyond that it streams through an L2-resident workspace in [row][contact] order
-// (lcp_contact_forward_kernel); any other n <= 64 falls back to an LU in LDS.  Sums over contacts (K = Q + sum P C P^T, the
-// gathers G^T u) are formed by lanes that each own a piece of a (body1, body2) run of contacts and add their partial sums with
-// LDS atomics -- one wavefront, one instruction stream, so the order of the additions is fixed: results are bitwise
-// reproducible run to run (tested at B = 1024), though not in contact order any more.
+// Mapping: blockDim = 64 (one wave) per scene, one forward kernel (lcp_contact_forward_kernel<ND, N, CPL>).  LDS: H = Q +
+// sum P C P^T (odd leading dimension => conflict free column walks), contact points, per-contact 3-vectors / C matrices,
+// nz-sized vectors.  The compiled system sizes (n = 54: 8 bodies + 6 equality rows; n = 18) are factored with one matrix row
+// per lane in registers (kkt_reg.h); any other n <= 64 falls back to an LU in LDS.  The per-contact IPM state (s, z, rz, ds,
+// dz, d: NR doubles each) of two contacts per lane lives in registers with maxc <= 128 (CPL = 2; there a body pinned by
+// identity equality rows is eliminated in closed form first), and streams through an L2-resident workspace in [row][contact]
+// order beyond (CPL = 0).  Sums over contacts (K = Q + sum P C P^T, the gathers G^T u) are formed by lanes that each own a
+// piece of a (body1, body2) run of contacts and add their partial sums with LDS atomics -- one wavefront, one instruction
+// stream.  Results have been bitwise reproducible run to run in tests (B = 1024), i.e. the hardware has served the lanes
+// that meet at an LDS address in a fixed order; no hardware document promises that order.  The sums are not in contact
+// order.
 #include <math.h>
 
 #include "../../include/diffsdfsim_hip.h"
@@ -536,7 +537,25 @@ struct StepAcc {
     }
 };
 
-template <int ND>
+enum { ST_s, ST_z, ST_rz, ST_ds, ST_dz, ST_d, ST_FIELDS };   // fields of the IPM state, in workspace order
+// the NR rows of one contact in one field of the streamed IPM state
+template <int NR> __device__ inline double *load_rows(double *o, const double *f, int maxc, int c)
+{
+#pragma unroll
+    for (int q = 0; q < NR; ++q) o[q] = f[(size_t)q * maxc + c];
+    return o;
+}
+
+// The forward solve, one wavefront per scene, written once for both places the per-contact state can live.
+//   ND  = friction directions / 2.
+//   N   = compiled size of the register-resident factorisation (54, 18): its factored rows stay in registers from the affine
+//         solve to the corrector solve of an iteration.  N = 0: kkt_factor_solve chooses by n (register rows parked in L.kf
+//         between the two solves for n = 54, 18; the LDS LU for any other n <= 64).
+//   CPL = contacts per lane held in registers: 2 (maxc <= 128) or 0 = the state streams through the workspace (any maxc).
+// Inside the iteration nothing but the contact operands and the state is read from memory, d = z/s is divided out once per
+// iteration, and sum(s z) after the affine step needs no pass.  The two state forms run the same expressions in the same
+// order between the same barriers, so they give the same results (the emulator: bitwise; tests/test_emu_lcp_contact.py).
+template <int ND, int N, int CPL>
 __global__ void __launch_bounds__(64)
 lcp_contact_forward_kernel(const double *Mblk_, const double *pvec_, const double *A_, const double *bvec_,
                            const double *cop_, const int *cbody_, const int *ncs, const int *active, int nb, int neq,
@@ -544,6 +563,7 @@ lcp_contact_forward_kernel(const double *Mblk_, const double *pvec_, const doubl
                            double *slack_, double *nu_, int *iters, int *status, double *ws_)
 {
     constexpr int NR = Geo<ND>::NR, NF = Geo<ND>::NF;
+    static_assert(CPL == 2 || (CPL == 0 && N == 0), "streamed state takes kkt_factor_solve");
     DSS_DYN_LDS(double, ldsmem);
     const int sc = blockIdx.x, lane = lane_id();
     if (active && !active[sc]) return;
@@ -556,14 +576,33 @@ lcp_contact_forward_kernel(const double *Mblk_, const double *pvec_, const doubl
     const int *cbody = cbody_ + (size_t)sc * 2 * maxc;
     double *x_out = x_out_ + (size_t)sc * nz, *lam = lam_ + (size_t)sc * NR * maxc, *slack = slack_ + (size_t)sc * NR * maxc;
     double *nu = neq ? nu_ + (size_t)sc * neq : nullptr;
-    double *ws = ws_ + (size_t)sc * (5 * NR * maxc + 64 * 64);
-    L.kf = ws + (size_t)5 * NR * maxc;
+    double *ws = ws_ + (size_t)sc * (ST_FIELDS * NR * maxc + 64 * 64);
+    L.kf = N > 0 ? nullptr : ws + (size_t)ST_FIELDS * NR * maxc;
     L.Ag = A;
-    double *cs = ws, *cz = ws + (size_t)NR * maxc, *crz = ws + (size_t)2 * NR * maxc, *cds = ws + (size_t)3 * NR * maxc,
-           *cdz = ws + (size_t)4 * NR * maxc;
     int nc = ncs[sc];
     if (nc > maxc) nc = maxc;
     const int nineq = nc * NR;
+    // The per-contact IPM state: s, z, rz, ds, dz and d = z/s, NR doubles each per contact.  Lane l owns the contacts c = l + 64 r.
+    //   CPL = 2 (maxc <= 128): these registers, r = 0, 1.  Every loop over r is unrolled, so every index is known at compile time
+    //            (an array indexed at run time would live in scratch memory).
+    //   CPL = 0 (any maxc): the workspace, [field][row][contact] (neighbouring lanes side by side), reached by c; r runs to the
+    //            lane's number of contacts.
+    // ST(f, r, c, q) is row q of field f of contact c = lane + 64 r; the loops over r skip a contact that is not there with ST_ON(r).
+    // (The locals of the register form -- which passes name c, the order of it / not_improved / have_best / best and of
+    //  acc_sz / acc_rz -- are those of the register kernel this body replaced: they set the order in which the compiler
+    //  promotes the arrays to registers, and the register allocation of the compiled sizes follows it.  With them the ISA of
+    //  <ND, 54 | 18, 2> is that of the former kernel; other orders cost <4, 54, 2> four more spilled VGPRs.)
+    constexpr int RC = CPL > 0 ? CPL : 1;
+    double sv[RC][NR], zv[RC][NR], rzv[RC][NR], dsv[RC][NR], dzv[RC][NR], dv[RC][NR];
+    bool valid[RC];
+    double rows[ST_FIELDS][NR];   // (CPL = 0) ST_ROW's copies
+#pragma unroll
+    for (int r = 0; r < RC; ++r) valid[r] = lane + WAVE * r < nc;
+    const int rounds = CPL > 0 ? CPL : (nc - lane + WAVE - 1) / WAVE;
+#define ST(f, r, c, q) (CPL > 0 ? f##v[r][q] : ws[(size_t)(ST_##f * NR + (q)) * maxc + (c)])
+#define ST_ON(r) (CPL == 0 || valid[r])
+    // ST_ROW(f, r, c): the NR rows of a field as an array -- the registers themselves, or a copy of the workspace rows in rows[f]
+#define ST_ROW(f, r, c) (CPL > 0 ? f##v[r] : load_rows<NR>(rows[ST_##f], ws + (size_t)ST_##f * NR * maxc, maxc, c))
 
     for (int i = lane; i < nz; i += WAVE) L.pl[i] = pvec[i];
     for (int c = lane; c < nc; c += WAVE) {
@@ -575,345 +614,35 @@ lcp_contact_forward_kernel(const double *Mblk_, const double *pvec_, const doubl
     build_lists(L, cbody, nc);
 
     // ---- initial point: d = 1  (batch.py:85-110) -------------------------------------------
-    for (int c = lane; c < nc; c += WAVE) {
-        Geo<ND> g;
-        load_geo<ND>(g, cop, cbody, maxc, c);
-        double a[NR], t[NR], u[NR], w[3], C[9];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) { a[r] = 1.0; t[r] = 0.0; }
-        t[0] = -g.hn;  // rz - rs/d with rz = -h, rs = 0
-        w_apply<ND>(g.mu, a, 1.0, t, u);
-        w_vec<ND>(g, u, w);
-        c_mat<ND>(g, a, 1.0, C);
-        // the C matrices go to K first; stash w in the (not yet used) ds scratch
-#pragma unroll
-        for (int j = 0; j < 9; ++j) L.cw[9 * c + j] = C[j];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) cds[(size_t)j * maxc + c] = w[j];
-    }
-    __syncthreads();
-    assemble_K(L, Mblk, A, cbody, nc);
-    for (int c = lane; c < nc; c += WAVE)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) L.cw[3 * c + j] = cds[(size_t)j * maxc + c];
-    __syncthreads();
-    gather<1>(L, L.g1, nullptr);
+    // the C matrices go to K first; w waits in registers (CPL = 2) or in the not yet used ds slots
     {
-        double rhs = 0.0;
-        if (lane < nz) rhs = -L.pl[lane] - L.g1[lane];
-        else if (lane < n) rhs = bvec[lane - nz];
-        const double sol = kkt_factor_solve(L, rhs);
-        if (lane < n) L.xv[lane] = sol;
-    }
-    __syncthreads();
-    if (nc == 0) {  // no complementarity conditions: the linear solve is the answer (engines.py:40-54)
-        if (lane < nz) x_out[lane] = L.xv[lane];
-        else if (lane < n) nu[lane - nz] = L.xv[lane];
-        if (lane == 0) { iters[sc] = 0; status[sc] = DSS_LCP_OK; }
-        return;
-    }
-    {
-        double mins = INFINITY, minz = INFINITY;
-        for (int c = lane; c < nc; c += WAVE) {
-            Geo<ND> g;
-            load_geo<ND>(g, cop, cbody, maxc, c);
-            double a[NR], r[NR], u[NR], vr[3];
-            rel_vel<ND>(L.xv, g, vr);
-            g_rows<ND>(g, vr, r);
-            r[0] -= g.hn;
-#pragma unroll
-            for (int q = 0; q < NR; ++q) a[q] = 1.0;
-            w_apply<ND>(g.mu, a, 1.0, r, u);
-#pragma unroll
-            for (int q = 0; q < NR; ++q) {
-                cz[(size_t)q * maxc + c] = u[q];
-                cs[(size_t)q * maxc + c] = -u[q];
-                minz = fmin(minz, u[q]);
-                mins = fmin(mins, -u[q]);
-            }
-        }
-        mins = wave_min_dpp(mins);
-        minz = wave_min_dpp(minz);
-        __syncthreads();
-        for (int c = lane; c < nc; c += WAVE)
-#pragma unroll
-            for (int q = 0; q < NR; ++q) {
-                if (mins < 0) cs[(size_t)q * maxc + c] -= mins - 1.0;
-                if (minz < 0) cz[(size_t)q * maxc + c] -= minz - 1.0;
-            }
-        __syncthreads();
-    }
-
-    double best = 0.0;
-    int have_best = 0, not_improved = 0, it = 0;
-    LSTAMP_INIT;
-    LSTAMP(0);
-    for (it = 0; it < max_iter; ++it) {
-        // ---- residuals (batch.py:117-131) and the affine right-hand side ---------------------
-        double acc_rz = 0.0, acc_sz = 0.0;
-        for (int c = opaque_lane(lane); c < nc; c += WAVE) {
-            Geo<ND> g;
-            load_geo<ND>(g, cop, cbody, maxc, c);
-            double s[NR], z[NR], gx[NR], fz[NR], a[NR], t[NR], u[NR], vr[3], w[3];
-#pragma unroll
-            for (int q = 0; q < NR; ++q) { s[q] = cs[(size_t)q * maxc + c]; z[q] = cz[(size_t)q * maxc + c]; }
-            rel_vel<ND>(L.xv, g, vr);
-            g_rows<ND>(g, vr, gx);
-            f_rows<ND>(g.mu, z, fz);
-#pragma unroll
-            for (int q = 0; q < NR; ++q) {
-                const double rz = gx[q] + s[q] - (q == 0 ? g.hn : 0.0) - fz[q];
-                crz[(size_t)q * maxc + c] = rz;
-                acc_rz += rz * rz;
-                acc_sz += s[q] * z[q];
-                a[q] = z[q] / s[q];   // 1/a = d
-                t[q] = rz - s[q];  // rz - rs/d with rs = z
-            }
-            w_vec<ND>(g, z, w);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) L.cw[6 * c + j] = w[j];
-            w_apply<ND>(g.mu, a, s[NR - 1] / z[NR - 1], t, u);
-            w_vec<ND>(g, u, w);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) L.cw[6 * c + 3 + j] = w[j];
-        }
-        acc_rz = wave_sum(acc_rz);
-        const double sz = wave_sum(acc_sz);
-        __syncthreads();
-        LSTAMP(1);
-        gather<2>(L, L.g1, L.g2);  // g1 = G^T z, g2 = G^T W (rz - s)
-        LSTAMP(2);
-        double rx = 0.0, ry = 0.0;
-        if (lane < nz) {
-            rx = q_times(Mblk, L.xv, lane) + L.pl[lane] + L.g1[lane];
-            for (int e = 0; e < neq; ++e) rx += A[e * nz + lane] * L.xv[nz + e];
-        } else if (lane < n) {
-            const int e = lane - nz;
-            for (int j = 0; j < nz; ++j) ry += A[e * nz + j] * L.xv[j];
-            ry -= bvec[e];
-        }
-        const double nrx = sqrt(wave_sum(rx * rx)), nry = sqrt(wave_sum(ry * ry));
-        const double mu = fabs(sz / nineq);
-        const double resid = sqrt(acc_rz) + nry + nrx + nineq * mu;
-        if (!have_best || resid < best) {
-            best = resid; have_best = 1; not_improved = 0;
-            if (lane < nz) x_out[lane] = L.xv[lane];
-            else if (lane < n) nu[lane - nz] = L.xv[lane];
-            for (int c = opaque_lane(lane); c < nc; c += WAVE)
-#pragma unroll
-                for (int q = 0; q < NR; ++q) {
-                    lam[(size_t)q * maxc + c] = cz[(size_t)q * maxc + c];
-                    slack[(size_t)q * maxc + c] = cs[(size_t)q * maxc + c];
-                }
-        } else {
-            ++not_improved;
-        }
-        if (not_improved == not_improved_lim || best < eps || mu > 1e32) break;
-        LSTAMP(3);
-
-        // ---- K(d) and the affine direction (batch.py:135,174) --------------------------------
-        __syncthreads();
-        for (int c = opaque_lane(lane); c < nc; c += WAVE) {
-            Geo<ND> g;
-            load_geo<ND>(g, cop, cbody, maxc, c);
-            double a[NR], C[9];
-#pragma unroll
-            for (int q = 0; q < NR; ++q) a[q] = cz[(size_t)q * maxc + c] / cs[(size_t)q * maxc + c];
-            c_mat<ND>(g, a, cs[(size_t)(NR - 1) * maxc + c] / cz[(size_t)(NR - 1) * maxc + c], C);
-#pragma unroll
-            for (int j = 0; j < 9; ++j) L.cw[9 * c + j] = C[j];
-        }
-        __syncthreads();
-        LSTAMP(4);
-        assemble_K(L, Mblk, A, cbody, nc);
-        LSTAMP(5);
-        LSTAMP(6);
-        {
-            double rhs = 0.0;
-            if (lane < nz) rhs = -rx - L.g2[lane];
-            else if (lane < n) rhs = -ry;
-            const double sol = kkt_factor_solve(L, rhs);
-            if (lane < n) L.dxa[lane] = sol;
-        }
-        __syncthreads();
-        LSTAMP(7);
-        StepAcc stz, sts;
-        for (int c = opaque_lane(lane); c < nc; c += WAVE) {
-            Geo<ND> g;
-            load_geo<ND>(g, cop, cbody, maxc, c);
-            double s[NR], z[NR], a[NR], r[NR], u[NR], vr[3];
-            rel_vel<ND>(L.dxa, g, vr);
-            g_rows<ND>(g, vr, r);
-#pragma unroll
-            for (int q = 0; q < NR; ++q) {
-                s[q] = cs[(size_t)q * maxc + c]; z[q] = cz[(size_t)q * maxc + c];
-                a[q] = z[q] / s[q];
-                r[q] += crz[(size_t)q * maxc + c] - s[q];
-            }
-            w_apply<ND>(g.mu, a, s[NR - 1] / z[NR - 1], r, u);
-#pragma unroll
-            for (int q = 0; q < NR; ++q) {
-                const double dz = u[q], ds = (-z[q] - dz) / a[q];
-                cdz[(size_t)q * maxc + c] = dz;
-                cds[(size_t)q * maxc + c] = ds;
-                stz.add(z[q], dz);
-                sts.add(s[q], ds);
-            }
-        }
-        double alpha = fmin(fmin(stz.finish(), sts.finish()), 1.0);
-        __syncthreads();
-        LSTAMP(8);
-        double t3 = 0.0;
-        for (int c = opaque_lane(lane); c < nc; c += WAVE)
-#pragma unroll
-            for (int q = 0; q < NR; ++q)
-                t3 += (cs[(size_t)q * maxc + c] + alpha * cds[(size_t)q * maxc + c]) *
-                      (cz[(size_t)q * maxc + c] + alpha * cdz[(size_t)q * maxc + c]);
-        t3 = wave_sum(t3);
-        double sig = t3 / sz;
-        sig = sig * sig * sig;
-        // ---- corrector (batch.py:194-205): rx = rz = ry = 0, rs = (-mu sig + ds dz)/s ----------
-        for (int c = opaque_lane(lane); c < nc; c += WAVE) {
-            Geo<ND> g;
-            load_geo<ND>(g, cop, cbody, maxc, c);
-            double a[NR], t[NR], u[NR], w[3], ag = 1.0;
-#pragma unroll
-            for (int q = 0; q < NR; ++q) {
-                const double s = cs[(size_t)q * maxc + c], z = cz[(size_t)q * maxc + c];
-                const double rs2 = (-mu * sig + cds[(size_t)q * maxc + c] * cdz[(size_t)q * maxc + c]) / s;
-                a[q] = z / s;
-                t[q] = rs2 / a[q];
-                if (q == NR - 1) ag = s / z;
-            }
-            w_apply<ND>(g.mu, a, ag, t, u);
-            w_vec<ND>(g, u, w);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) L.cw[3 * c + j] = w[j];
-        }
-        __syncthreads();
-        LSTAMP(9);
-        gather<1>(L, L.g1, nullptr);
-        {
-            double rhs = (lane < nz) ? L.g1[lane] : 0.0;
-            const double sol = kkt_solve(L, rhs);
-            if (lane < n) L.sol[lane] = sol;
-        }
-        __syncthreads();
-        LSTAMP(10);
-        StepAcc stz2, sts2;
-        for (int c = opaque_lane(lane); c < nc; c += WAVE) {
-            Geo<ND> g;
-            load_geo<ND>(g, cop, cbody, maxc, c);
-            double s[NR], z[NR], a[NR], r[NR], u[NR], rs2[NR], vr[3];
-            rel_vel<ND>(L.sol, g, vr);
-            g_rows<ND>(g, vr, r);
-#pragma unroll
-            for (int q = 0; q < NR; ++q) {
-                s[q] = cs[(size_t)q * maxc + c]; z[q] = cz[(size_t)q * maxc + c];
-                rs2[q] = (-mu * sig + cds[(size_t)q * maxc + c] * cdz[(size_t)q * maxc + c]) / s[q];
-                a[q] = z[q] / s[q];
-                r[q] -= rs2[q] / a[q];
-            }
-            w_apply<ND>(g.mu, a, s[NR - 1] / z[NR - 1], r, u);
-#pragma unroll
-            for (int q = 0; q < NR; ++q) {
-                const double dz = cdz[(size_t)q * maxc + c] + u[q];
-                const double ds = cds[(size_t)q * maxc + c] + (-rs2[q] - u[q]) / a[q];
-                cdz[(size_t)q * maxc + c] = dz;
-                cds[(size_t)q * maxc + c] = ds;
-                stz2.add(z[q], dz);
-                sts2.add(s[q], ds);
-            }
-        }
-        alpha = fmin(0.999 * fmin(stz2.finish(), sts2.finish()), 1.0);
-        __syncthreads();
-        LSTAMP(11);
-        if (lane < n) L.xv[lane] += alpha * (L.dxa[lane] + L.sol[lane]);
-        for (int c = opaque_lane(lane); c < nc; c += WAVE)
-#pragma unroll
-            for (int q = 0; q < NR; ++q) {
-                cs[(size_t)q * maxc + c] += alpha * cds[(size_t)q * maxc + c];
-                cz[(size_t)q * maxc + c] += alpha * cdz[(size_t)q * maxc + c];
-            }
-        __syncthreads();
-        LSTAMP(12);
-    }
-    if (lane == 0) { iters[sc] = it; status[sc] = (best > 1.0) ? DSS_LCP_INACCURATE : DSS_LCP_OK; }
-}
-
-// The same solver with the per-contact IPM state (s, z, rz, ds, dz, d = z/s) held in registers: lane l owns contacts
-// l and l + 64 (maxc <= 128), every loop over them is unrolled with compile-time indices.  Nothing but the contact
-// operands is re-read from memory inside the iteration, d is divided out once per iteration instead of once per
-// pass, and sum(s z) after the affine step needs no pass at all.  Arithmetic per contact is expression for
-// expression that of lcp_contact_forward_kernel (the streaming form, kept for maxc > 128): results are bit-identical.
-// N = compiled size of the register-resident factorisation (54, 18) or 0 = LDS fallback for other n <= 64.  With
-// N > 0 the factored rows stay in registers from the affine solve to the corrector solve of the same iteration.
-template <int ND, int N>
-__global__ void __launch_bounds__(64)
-lcp_contact_forward_reg_kernel(const double *Mblk_, const double *pvec_, const double *A_, const double *bvec_,
-                               const double *cop_, const int *cbody_, const int *ncs, const int *active, int nb, int neq,
-                               int maxc, double eps, int not_improved_lim, int max_iter, double *x_out_, double *lam_,
-                               double *slack_, double *nu_, int *iters, int *status, double *ws_)
-{
-    constexpr int NR = Geo<ND>::NR, NF = Geo<ND>::NF, CPL = 2;
-    DSS_DYN_LDS(double, ldsmem);
-    const int sc = blockIdx.x, lane = lane_id();
-    if (active && !active[sc]) return;
-    Lds L;
-    carve_lds(L, ldsmem, nb, neq, maxc);
-    const int nz = L.nz, n = L.n;
-    const double *Mblk = Mblk_ + (size_t)sc * nb * 36, *pvec = pvec_ + (size_t)sc * nz;
-    const double *A = neq ? A_ + (size_t)sc * neq * nz : nullptr, *bvec = neq ? bvec_ + (size_t)sc * neq : nullptr;
-    const double *cop = cop_ + (size_t)sc * NF * maxc;
-    const int *cbody = cbody_ + (size_t)sc * 2 * maxc;
-    double *x_out = x_out_ + (size_t)sc * nz, *lam = lam_ + (size_t)sc * NR * maxc, *slack = slack_ + (size_t)sc * NR * maxc;
-    double *nu = neq ? nu_ + (size_t)sc * neq : nullptr;
-    L.kf = N > 0 ? nullptr : ws_ + (size_t)sc * (5 * NR * maxc + 64 * 64) + (size_t)5 * NR * maxc;
-    L.Ag = A;
-    int nc = ncs[sc];
-    if (nc > maxc) nc = maxc;
-    const int nineq = nc * NR;
-
-    double s[CPL][NR], z[CPL][NR], rzv[CPL][NR], dsv[CPL][NR], dzv[CPL][NR], av[CPL][NR];
-    bool valid[CPL];
-#pragma unroll
-    for (int r = 0; r < CPL; ++r) valid[r] = lane + WAVE * r < nc;
-
-    for (int i = lane; i < nz; i += WAVE) L.pl[i] = pvec[i];
-    for (int c = lane; c < nc; c += WAVE) {
-        const int o = 3 * (1 + ND);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) L.pbuf[6 * c + j] = cop[(size_t)(o + j) * maxc + c];
-    }
-    __syncthreads();
-    build_lists(L, cbody, nc);
-
-    // ---- initial point: d = 1  (batch.py:85-110) -------------------------------------------
-    {
-        double w0[CPL][3];
-#pragma unroll
-        for (int r = 0; r < CPL; ++r) {
+        double w0[RC][3];
+#pragma unroll RC
+        for (int r = 0; r < rounds; ++r) {
             const int c = lane + WAVE * r;
-            if (!valid[r]) continue;
+            if (!ST_ON(r)) continue;
             Geo<ND> g;
             load_geo<ND>(g, cop, cbody, maxc, c);
-            double a[NR], t[NR], u[NR], C[9];
+            double a[NR], t[NR], u[NR], w[3], C[9];
 #pragma unroll
             for (int q = 0; q < NR; ++q) { a[q] = 1.0; t[q] = 0.0; }
             t[0] = -g.hn;  // rz - rs/d with rz = -h, rs = 0
             w_apply<ND>(g.mu, a, 1.0, t, u);
-            w_vec<ND>(g, u, w0[r]);
+            w_vec<ND>(g, u, w);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) (CPL > 0 ? w0[r][j] : ST(ds, r, c, j)) = w[j];
             c_mat<ND>(g, a, 1.0, C);
 #pragma unroll
             for (int j = 0; j < 9; ++j) L.cw[9 * c + j] = C[j];
         }
         __syncthreads();
         assemble_K(L, Mblk, A, cbody, nc);
+#pragma unroll RC
+        for (int r = 0; r < rounds; ++r)
+            if (ST_ON(r))
 #pragma unroll
-        for (int r = 0; r < CPL; ++r)
-            if (valid[r])
-#pragma unroll
-                for (int j = 0; j < 3; ++j) L.cw[3 * (lane + WAVE * r) + j] = w0[r][j];
+                for (int j = 0; j < 3; ++j)
+                    L.cw[3 * (lane + WAVE * r) + j] = CPL > 0 ? w0[r][j] : ST(ds, r, lane + WAVE * r, j);
         __syncthreads();
     }
     gather<1>(L, L.g1, nullptr);
@@ -933,9 +662,9 @@ lcp_contact_forward_reg_kernel(const double *Mblk_, const double *pvec_, const d
     }
     {
         double mins = INFINITY, minz = INFINITY;
-#pragma unroll
-        for (int r = 0; r < CPL; ++r) {
-            if (!valid[r]) continue;
+#pragma unroll RC
+        for (int r = 0; r < rounds; ++r) {
+            if (!ST_ON(r)) continue;
             Geo<ND> g;
             load_geo<ND>(g, cop, cbody, maxc, lane + WAVE * r);
             double a[NR], rr[NR], u[NR], vr[3];
@@ -947,20 +676,20 @@ lcp_contact_forward_reg_kernel(const double *Mblk_, const double *pvec_, const d
             w_apply<ND>(g.mu, a, 1.0, rr, u);
 #pragma unroll
             for (int q = 0; q < NR; ++q) {
-                z[r][q] = u[q];
-                s[r][q] = -u[q];
+                ST(z, r, lane + WAVE * r, q) = u[q];
+                ST(s, r, lane + WAVE * r, q) = -u[q];
                 minz = fmin(minz, u[q]);
                 mins = fmin(mins, -u[q]);
             }
         }
         mins = wave_min_dpp(mins);
         minz = wave_min_dpp(minz);
-#pragma unroll
-        for (int r = 0; r < CPL; ++r)
+#pragma unroll RC
+        for (int r = 0; r < rounds; ++r)
 #pragma unroll
             for (int q = 0; q < NR; ++q) {
-                if (mins < 0) s[r][q] -= mins - 1.0;
-                if (minz < 0) z[r][q] -= minz - 1.0;
+                if (mins < 0) ST(s, r, lane + WAVE * r, q) -= mins - 1.0;
+                if (minz < 0) ST(z, r, lane + WAVE * r, q) -= minz - 1.0;
             }
     }
 
@@ -990,38 +719,39 @@ lcp_contact_forward_reg_kernel(const double *Mblk_, const double *pvec_, const d
         pinned0 = tri;
     }
 
+    int it = 0, not_improved = 0, have_best = 0;
     double best = 0.0;
-    int have_best = 0, not_improved = 0, it = 0;
     LSTAMP_INIT;
     LSTAMP(0);
     for (it = 0; it < max_iter; ++it) {
         // ---- residuals (batch.py:117-131), the affine right-hand side and K(d) ------------------
-        double acc_rz = 0.0, acc_sz = 0.0;
+        double acc_sz = 0.0, acc_rz = 0.0;
         const int l0 = opaque_lane(lane);
-#pragma unroll
-        for (int r = 0; r < CPL; ++r) {
+#pragma unroll RC
+        for (int r = 0; r < rounds; ++r) {
             const int c = l0 + WAVE * r;
-            if (!valid[r]) continue;
+            if (!ST_ON(r)) continue;
             Geo<ND> g;
             load_geo<ND>(g, cop, cbody, maxc, c);
             double gx[NR], fz[NR], t[NR], u[NR], vr[3], w[3];
+            const double *s = ST_ROW(s, r, c), *z = ST_ROW(z, r, c);
             rel_vel<ND>(L.xv, g, vr);
             g_rows<ND>(g, vr, gx);
-            f_rows<ND>(g.mu, z[r], fz);
+            f_rows<ND>(g.mu, z, fz);
 #pragma unroll
             for (int q = 0; q < NR; ++q) {
-                const double rz = gx[q] + s[r][q] - (q == 0 ? g.hn : 0.0) - fz[q];
-                rzv[r][q] = rz;
+                const double rz = gx[q] + s[q] - (q == 0 ? g.hn : 0.0) - fz[q];
+                ST(rz, r, c, q) = rz;
                 acc_rz += rz * rz;
-                acc_sz += s[r][q] * z[r][q];
-                av[r][q] = z[r][q] / s[r][q];   // 1/a = d
-                t[q] = rz - s[r][q];            // rz - rs/d with rs = z
+                acc_sz += s[q] * z[q];
+                ST(d, r, c, q) = z[q] / s[q];   // 1/a = d
+                t[q] = rz - s[q];               // rz - rs/d with rs = z
             }
-            w_vec<ND>(g, z[r], w);
+            w_vec<ND>(g, z, w);
 #pragma unroll
             for (int j = 0; j < 3; ++j) L.cw[6 * c + j] = w[j];
-            const double ag = s[r][NR - 1] / z[r][NR - 1];
-            w_apply<ND>(g.mu, av[r], ag, t, u);
+            const double ag = s[NR - 1] / z[NR - 1];
+            w_apply<ND>(g.mu, ST_ROW(d, r, c), ag, t, u);
             w_vec<ND>(g, u, w);
 #pragma unroll
             for (int j = 0; j < 3; ++j) L.cw[6 * c + 3 + j] = w[j];
@@ -1051,13 +781,13 @@ lcp_contact_forward_reg_kernel(const double *Mblk_, const double *pvec_, const d
             best = resid; have_best = 1; not_improved = 0;
             if (lane < nz) x_out[lane] = L.xv[lane];
             else if (lane < n) nu[lane - nz] = L.xv[lane];
-#pragma unroll
-            for (int r = 0; r < CPL; ++r)
-                if (valid[r])
+#pragma unroll RC
+            for (int r = 0; r < rounds; ++r)
+                if (ST_ON(r))
 #pragma unroll
                     for (int q = 0; q < NR; ++q) {
-                        lam[(size_t)q * maxc + l0 + WAVE * r] = z[r][q];
-                        slack[(size_t)q * maxc + l0 + WAVE * r] = s[r][q];
+                        lam[(size_t)q * maxc + l0 + WAVE * r] = ST(z, r, l0 + WAVE * r, q);
+                        slack[(size_t)q * maxc + l0 + WAVE * r] = ST(s, r, l0 + WAVE * r, q);
                     }
         } else {
             ++not_improved;
@@ -1069,13 +799,14 @@ lcp_contact_forward_reg_kernel(const double *Mblk_, const double *pvec_, const d
         __syncthreads();
         // the contacts' C matrices, formed here rather than carried in registers (18 doubles per lane) through the gathers
         // and the residual block above: the operands come from L2 again, the registers are what this kernel is short of
-#pragma unroll
-        for (int r = 0; r < CPL; ++r)
-            if (valid[r]) {
+#pragma unroll RC
+        for (int r = 0; r < rounds; ++r)
+            if (ST_ON(r)) {
                 Geo<ND> g;
                 load_geo<ND>(g, cop, cbody, maxc, l0 + WAVE * r);
                 double C[9];
-                c_mat<ND>(g, av[r], s[r][NR - 1] / z[r][NR - 1], C);
+                c_mat<ND>(g, ST_ROW(d, r, l0 + WAVE * r), ST(s, r, l0 + WAVE * r, NR - 1) / ST(z, r, l0 + WAVE * r, NR - 1),
+                          C);
 #pragma unroll
                 for (int j = 0; j < 9; ++j) L.cw[9 * (l0 + WAVE * r) + j] = C[j];
             }
@@ -1132,53 +863,59 @@ lcp_contact_forward_reg_kernel(const double *Mblk_, const double *pvec_, const d
         LSTAMP(7);
         StepAcc stz, sts;
         const int l1 = opaque_lane(lane);
-#pragma unroll
-        for (int r = 0; r < CPL; ++r) {
-            if (!valid[r]) continue;
+#pragma unroll RC
+        for (int r = 0; r < rounds; ++r) {
+            if (!ST_ON(r)) continue;
             Geo<ND> g;
             load_geo<ND>(g, cop, cbody, maxc, l1 + WAVE * r);
             double rr[NR], u[NR], vr[3];
+            const double *s = ST_ROW(s, r, l1 + WAVE * r), *z = ST_ROW(z, r, l1 + WAVE * r), *d = ST_ROW(d, r, l1 + WAVE * r),
+                         *rz = ST_ROW(rz, r, l1 + WAVE * r);
             rel_vel<ND>(L.dxa, g, vr);
             g_rows<ND>(g, vr, rr);
 #pragma unroll
-            for (int q = 0; q < NR; ++q) rr[q] += rzv[r][q] - s[r][q];
-            w_apply<ND>(g.mu, av[r], s[r][NR - 1] / z[r][NR - 1], rr, u);
+            for (int q = 0; q < NR; ++q) rr[q] += rz[q] - s[q];
+            w_apply<ND>(g.mu, d, s[NR - 1] / z[NR - 1], rr, u);
 #pragma unroll
             for (int q = 0; q < NR; ++q) {
-                const double dz = u[q], ds = (-z[r][q] - dz) / av[r][q];
-                dzv[r][q] = dz;
-                dsv[r][q] = ds;
-                stz.add(z[r][q], dz);
-                sts.add(s[r][q], ds);
+                const double dz = u[q], ds = (-z[q] - dz) / d[q];
+                ST(dz, r, l1 + WAVE * r, q) = dz;
+                ST(ds, r, l1 + WAVE * r, q) = ds;
+                stz.add(z[q], dz);
+                sts.add(s[q], ds);
             }
         }
         double alpha = fmin(fmin(stz.finish(), sts.finish()), 1.0);
         LSTAMP(8);
         double t3 = 0.0;
+#pragma unroll RC
+        for (int r = 0; r < rounds; ++r)
+            if (ST_ON(r))
 #pragma unroll
-        for (int r = 0; r < CPL; ++r)
-            if (valid[r])
-#pragma unroll
-                for (int q = 0; q < NR; ++q) t3 += (s[r][q] + alpha * dsv[r][q]) * (z[r][q] + alpha * dzv[r][q]);
+                for (int q = 0; q < NR; ++q)
+                    t3 += (ST(s, r, l1 + WAVE * r, q) + alpha * ST(ds, r, l1 + WAVE * r, q)) *
+                          (ST(z, r, l1 + WAVE * r, q) + alpha * ST(dz, r, l1 + WAVE * r, q));
         t3 = wave_sum(t3);
         double sig = t3 / sz;
         sig = sig * sig * sig;
         // ---- corrector (batch.py:194-205): rx = rz = ry = 0, rs = (-mu sig + ds dz)/s ----------
         const int l2 = opaque_lane(lane);
-#pragma unroll
-        for (int r = 0; r < CPL; ++r) {
+#pragma unroll RC
+        for (int r = 0; r < rounds; ++r) {
             const int c = l2 + WAVE * r;
-            if (!valid[r]) continue;
+            if (!ST_ON(r)) continue;
             Geo<ND> g;
             load_geo<ND>(g, cop, cbody, maxc, c);
             double t[NR], u[NR], w[3];
+            const double *s = ST_ROW(s, r, c), *z = ST_ROW(z, r, c), *d = ST_ROW(d, r, c), *ds = ST_ROW(ds, r, c),
+                         *dz = ST_ROW(dz, r, c);
 #pragma unroll
             for (int q = 0; q < NR; ++q) {
-                const double rs2 = (-mu * sig + dsv[r][q] * dzv[r][q]) / s[r][q];
-                rzv[r][q] = rs2;                 // rz is not needed any more this iteration
-                t[q] = rs2 / av[r][q];
+                const double rs2 = (-mu * sig + ds[q] * dz[q]) / s[q];
+                ST(rz, r, c, q) = rs2;                 // rz is not needed any more this iteration
+                t[q] = rs2 / d[q];
             }
-            w_apply<ND>(g.mu, av[r], s[r][NR - 1] / z[r][NR - 1], t, u);
+            w_apply<ND>(g.mu, d, s[NR - 1] / z[NR - 1], t, u);
             w_vec<ND>(g, u, w);
 #pragma unroll
             for (int j = 0; j < 3; ++j) L.cw[3 * c + j] = w[j];
@@ -1210,43 +947,48 @@ lcp_contact_forward_reg_kernel(const double *Mblk_, const double *pvec_, const d
         LSTAMP(10);
         StepAcc stz2, sts2;
         const int l3 = opaque_lane(lane);
-#pragma unroll
-        for (int r = 0; r < CPL; ++r) {
-            if (!valid[r]) continue;
+#pragma unroll RC
+        for (int r = 0; r < rounds; ++r) {
+            if (!ST_ON(r)) continue;
             Geo<ND> g;
             load_geo<ND>(g, cop, cbody, maxc, l3 + WAVE * r);
             double rr[NR], u[NR], vr[3];
+            const double *s = ST_ROW(s, r, l3 + WAVE * r), *z = ST_ROW(z, r, l3 + WAVE * r), *d = ST_ROW(d, r, l3 + WAVE * r),
+                         *rs2 = ST_ROW(rz, r, l3 + WAVE * r);
             rel_vel<ND>(L.sol, g, vr);
             g_rows<ND>(g, vr, rr);
 #pragma unroll
-            for (int q = 0; q < NR; ++q) rr[q] -= rzv[r][q] / av[r][q];
-            w_apply<ND>(g.mu, av[r], s[r][NR - 1] / z[r][NR - 1], rr, u);
+            for (int q = 0; q < NR; ++q) rr[q] -= rs2[q] / d[q];
+            w_apply<ND>(g.mu, d, s[NR - 1] / z[NR - 1], rr, u);
 #pragma unroll
             for (int q = 0; q < NR; ++q) {
-                const double dz = dzv[r][q] + u[q];
-                const double ds = dsv[r][q] + (-rzv[r][q] - u[q]) / av[r][q];
-                dzv[r][q] = dz;
-                dsv[r][q] = ds;
-                stz2.add(z[r][q], dz);
-                sts2.add(s[r][q], ds);
+                const double dz = ST(dz, r, l3 + WAVE * r, q) + u[q];
+                const double ds = ST(ds, r, l3 + WAVE * r, q) + (-rs2[q] - u[q]) / d[q];
+                ST(dz, r, l3 + WAVE * r, q) = dz;
+                ST(ds, r, l3 + WAVE * r, q) = ds;
+                stz2.add(z[q], dz);
+                sts2.add(s[q], ds);
             }
         }
         alpha = fmin(0.999 * fmin(stz2.finish(), sts2.finish()), 1.0);
         __syncthreads();
         LSTAMP(11);
         if (lane < n) L.xv[lane] += alpha * (L.dxa[lane] + L.sol[lane]);
-#pragma unroll
-        for (int r = 0; r < CPL; ++r)
+#pragma unroll RC
+        for (int r = 0; r < rounds; ++r)
 #pragma unroll
             for (int q = 0; q < NR; ++q) {
-                s[r][q] += alpha * dsv[r][q];
-                z[r][q] += alpha * dzv[r][q];
+                ST(s, r, l3 + WAVE * r, q) += alpha * ST(ds, r, l3 + WAVE * r, q);
+                ST(z, r, l3 + WAVE * r, q) += alpha * ST(dz, r, l3 + WAVE * r, q);
             }
         __syncthreads();
         LSTAMP(12);
     }
     if (lane == 0) { iters[sc] = it; status[sc] = (best > 1.0) ? DSS_LCP_INACCURATE : DSS_LCP_OK; }
 }
+#undef ST
+#undef ST_ON
+#undef ST_ROW
 
 // Implicit backward (lcp.py:156-213) in the same reduced form; gradients come out already
 // contracted onto the contact operands (directions, contact points, mu, h_n), the mass blocks
@@ -1400,7 +1142,7 @@ extern "C" {
 size_t dss_lcp_contact_workspace_bytes(int B, int nb, int neq, int maxc, int fric_dirs)
 {
     if (!dims_ok(B, nb, neq, maxc, fric_dirs)) return 0;
-    return (size_t)B * (5 * (fric_dirs + 2) * maxc + 64 * 64) * sizeof(double);
+    return (size_t)B * (ST_FIELDS * (fric_dirs + 2) * maxc + 64 * 64) * sizeof(double);
 }
 
 int dss_lcp_contact_forward(const double *Mblk, const double *pvec, const double *A, const double *bvec,
@@ -1416,23 +1158,18 @@ int dss_lcp_contact_forward(const double *Mblk, const double *pvec, const double
     if (workspace_bytes < dss_lcp_contact_workspace_bytes(B, nb, neq, maxc, fric_dirs)) return DSS_E_WORKSPACE;
     const size_t lds = lds_bytes(nb, neq, maxc);
     if (lds > 64 * 1024) return DSS_E_UNSUPPORTED;
-    if (maxc <= 128) {   // two contacts per lane: IPM state in registers
-        const int n = 6 * nb + neq;
-#define DSS_LAUNCH_REG(ND_, N_)                                                                                         \
-        hipLaunchKernelGGL((lcp_contact_forward_reg_kernel<ND_, N_>), dim3(B), dim3(64), lds, (hipStream_t)stream, Mblk, pvec, \
-                           A, bvec, cop, cbody, nc, active, nb, neq, maxc, eps, not_improved_lim, max_iter, x, lam, slack, nu, \
-                           iters, status, (double *)workspace)
-        if (fric_dirs == 8) { if (n == 54) DSS_LAUNCH_REG(4, 54); else if (n == 18) DSS_LAUNCH_REG(4, 18); else DSS_LAUNCH_REG(4, 0); }
-        else { if (n == 54) DSS_LAUNCH_REG(2, 54); else if (n == 18) DSS_LAUNCH_REG(2, 18); else DSS_LAUNCH_REG(2, 0); }
-#undef DSS_LAUNCH_REG
-    } else if (fric_dirs == 8)
-        hipLaunchKernelGGL(lcp_contact_forward_kernel<4>, dim3(B), dim3(64), lds, (hipStream_t)stream, Mblk, pvec, A, bvec,
-                           cop, cbody, nc, active, nb, neq, maxc, eps, not_improved_lim, max_iter, x, lam, slack, nu, iters,
-                           status, (double *)workspace);
-    else
-        hipLaunchKernelGGL(lcp_contact_forward_kernel<2>, dim3(B), dim3(64), lds, (hipStream_t)stream, Mblk, pvec, A, bvec,
-                           cop, cbody, nc, active, nb, neq, maxc, eps, not_improved_lim, max_iter, x, lam, slack, nu, iters,
-                           status, (double *)workspace);
+    // maxc <= 128: two contacts per lane, IPM state in registers, N from n; beyond: the state streams through the workspace
+    const int n = 6 * nb + neq, N = maxc > 128 ? -1 : (n == 54 ? 54 : (n == 18 ? 18 : 0));
+#define DSS_LAUNCH(ND_, N_, CPL_)                                                                                               \
+    hipLaunchKernelGGL((lcp_contact_forward_kernel<ND_, N_, CPL_>), dim3(B), dim3(64), lds, (hipStream_t)stream, Mblk, pvec, A,  \
+                       bvec, cop, cbody, nc, active, nb, neq, maxc, eps, not_improved_lim, max_iter, x, lam, slack, nu, iters,   \
+                       status, (double *)workspace)
+    if (fric_dirs == 8) {
+        if (N == 54) DSS_LAUNCH(4, 54, 2); else if (N == 18) DSS_LAUNCH(4, 18, 2); else if (N == 0) DSS_LAUNCH(4, 0, 2); else DSS_LAUNCH(4, 0, 0);
+    } else {
+        if (N == 54) DSS_LAUNCH(2, 54, 2); else if (N == 18) DSS_LAUNCH(2, 18, 2); else if (N == 0) DSS_LAUNCH(2, 0, 2); else DSS_LAUNCH(2, 0, 0);
+    }
+#undef DSS_LAUNCH
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }
 

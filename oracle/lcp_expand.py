@@ -57,6 +57,16 @@ def random_problem(seed, B, nb, maxc, fd=8, nc_lo=1, nc_hi=None, fixed_body0=Tru
     return dict(Mblk=Mblk, pvec=pvec, A=A, bvec=bvec, cop=cop, cbody=cbody, nc=nc, nb=nb, neq=neq, maxc=maxc, fd=fd)
 
 
+
+def pad_contacts(P, maxc):
+    """The same problem with room for maxc contacts per scene (empty slots: zero operands, bodies 0 and 0)."""
+    Q = dict(P)
+    extra = maxc - P["maxc"]
+    Q["cop"] = np.concatenate([P["cop"], np.zeros(P["cop"].shape[:2] + (extra,))], 2)
+    Q["cbody"] = np.concatenate([P["cbody"], np.zeros(P["cbody"].shape[:2] + (extra,), np.int32)], 2)
+    Q["maxc"] = maxc
+    return Q
+
 def rows_of(cop_s, cbody_s, c, nb, fd):
     """The fd+2 dense G rows of contact c in structured row order [n, +D.., -D.., cone]."""
     ND = fd // 2

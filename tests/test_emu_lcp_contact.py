@@ -63,3 +63,22 @@ def test_block_tridiagonal_elimination_and_its_fallback_under_the_emulator():
         Q, p, G, h, A, b, F = S.expand_dense(P, s)
         zo = O.forward(Q[None], p[None], G[None], h[None], A[None], b[None], F[None], max_iter=10)[0]
         assert rel(x[s], zo[0]) < 1e-9, (s, rel(x[s], zo[0]))
+
+
+# (nb, fd, random_problem options): n = 6 nb + neq = 12 (no equality rows), 24, 30 (body 0 pinned), all through the LDS LU; and
+# n = 54 with contacts that do not form a chain, where both forms take the natural register factorisation
+STATE_FORMS = [(2, 8, dict(fixed_body0=False)), (3, 8, {}), (4, 8, {}), (2, 4, dict(fixed_body0=False)), (3, 4, {}),
+               (4, 4, {}), (8, 8, {})]
+
+
+@pytest.mark.parametrize("nb,fd,kw", STATE_FORMS)
+def test_register_and_streamed_state_agree(nb, fd, kw):
+    """One forward body, two places for the per-contact IPM state: registers (maxc <= 128) and the streamed workspace (the same
+    problem padded to maxc = 136).  The same expressions in the same order between the same barriers: bitwise equal."""
+    P = S.random_problem(seed=40 + nb + fd, B=2, nb=nb, maxc=128, fd=fd, nc_lo=40, **kw)
+    a = emu.lcp_contact_forward(P, max_iter=20)
+    b = emu.lcp_contact_forward(S.pad_contacts(P, 136), max_iter=20)
+    for k in (0, 3, 4, 5):      # x, nu, iters, status
+        assert np.array_equal(a[k], b[k]), k
+    for s, nc in enumerate(P["nc"]):
+        assert np.array_equal(a[1][s, :, :nc], b[1][s, :, :nc]) and np.array_equal(a[2][s, :, :nc], b[2][s, :, :nc])

@@ -52,6 +52,26 @@ def test_block_tridiagonal_elimination_and_its_fallback_agree_with_the_dense_ora
             assert rel(x[s], zo[0]) < 1e-9, (seed, s, rel(x[s], zo[0]))
 
 
+# (nb, fd, random_problem options) as in tests/test_emu_lcp_contact.py: n = 12, 24, 30 through the LDS LU, n = 54 with contacts that do
+# not form a chain (both forms: the natural register factorisation)
+STATE_FORMS = [(2, 8, dict(fixed_body0=False)), (3, 8, {}), (4, 8, {}), (2, 4, dict(fixed_body0=False)), (3, 4, {}),
+               (4, 4, {}), (8, 8, {})]
+
+
+@pytest.mark.parametrize("nb,fd,kw", STATE_FORMS)
+def test_register_and_streamed_state_agree(nb, fd, kw):
+    """The forward kernel with the per-contact IPM state in registers (maxc = 128) and streamed through the workspace (the same problem
+    padded to maxc = 136).  The emulator has them bitwise equal; on the device a value that goes through memory may meet an FMA that
+    the register form does not, so: the same iteration counts and status, results within 1e-12."""
+    P = S.random_problem(seed=40 + nb + fd, B=2, nb=nb, maxc=128, fd=fd, nc_lo=40, **kw)
+    a = [t.cpu().numpy() for t in run(P, max_iter=20)[1]]
+    b = [t.cpu().numpy() for t in run(S.pad_contacts(P, 136), max_iter=20)[1]]
+    assert np.array_equal(a[4], b[4]) and np.array_equal(a[5], b[5])
+    assert rel(b[0], a[0]) <= 1e-12 and rel(b[3], a[3]) <= 1e-12
+    for s, nc in enumerate(P["nc"]):
+        assert rel(b[1][s, :, :nc], a[1][s, :, :nc]) <= 1e-12 and rel(b[2][s, :, :nc], a[2][s, :, :nc]) <= 1e-12
+
+
 @pytest.mark.parametrize("cfg", [dict(seed=11, B=6, nb=2, maxc=8, fd=8), dict(seed=12, B=4, nb=8, maxc=32, fd=8),
                                  dict(seed=13, B=3, nb=3, maxc=8, fd=4), dict(seed=14, B=2, nb=4, maxc=96, fd=8, nc_lo=70),
                                  dict(seed=15, B=5, nb=2, maxc=8, fd=8), dict(seed=16, B=3, nb=8, maxc=24, fd=8, nc_lo=10),
