@@ -11,6 +11,21 @@ inline int dss_uniform(int x) { return x; }
 inline int dss_opaque(int x) { return x; }
 inline double dss_rcp(double x) { return 1.0 / x; }
 inline double dss_uniform(double x) { return x; }
+template <int CTRL> __device__ __forceinline__ double dss_dpp_mov(double x)
+{
+    const int l = threadIdx.x & 63, q = l & ~3, i = l & 3;
+    const int src = CTRL == 0x141 ? (l & ~7) | (7 - (l & 7)) : q | ((CTRL >> (2 * i)) & 3);
+    return __shfl(x, src, 64);
+}
+template <int CTRL> __device__ __forceinline__ int dss_dpp_movi(int x)
+{
+    const int l = threadIdx.x & 63, q = l & ~3, i = l & 3;
+    const int src = CTRL == 0x141 ? (l & ~7) | (7 - (l & 7)) : q | ((CTRL >> (2 * i)) & 3);
+    return __shfl(x, src, 64);
+}
+template <int J> __device__ __forceinline__ double dss_gbc(double x) { return __shfl(x, (threadIdx.x & (64 - 8)) | J, 64); }
+__device__ __forceinline__ double dss_wave_bcast(double x, int src_uniform) { return __shfl(x, src_uniform, 64); }
+__device__ inline double dss_wave_first(double x) { return __shfl(x, 0, 64); }
 #else
 #include <hip/hip_runtime.h>
 #define DSS_DYN_LDS(type, name) extern __shared__ __align__(16) type name[]
@@ -36,6 +51,31 @@ __device__ __forceinline__ int dss_uniform(int x) { return __builtin_amdgcn_read
 __device__ __forceinline__ double dss_uniform(double x)
 {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
+}
+// value of lane 0, for every lane (readfirstlane takes the first ACTIVE lane: lane 0 where the whole wavefront runs)
+__device__ inline double dss_wave_first(double x) { return dss_uniform(x); }
+// value of lane `src_uniform` (the same number in every lane), through scalar registers
+__device__ __forceinline__ double dss_wave_bcast(double x, int src_uniform)
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(x), src_uniform);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), src_uniform);
+    return __hiloint2double(hi, lo);
+}
+// Cross-lane moves with COMPILE-TIME partners on the DPP path of the vector ALU (a few cycles, against > 100 for ds_bpermute /
+// ds_swizzle through the LDS crossbar).  CTRL: a quad_perm pattern (partners inside a quad) or row_half_mirror (0x141: lane
+// i <-> 7 - i of every 8).
+template <int CTRL> __device__ __forceinline__ int dss_dpp_movi(int x) { return __builtin_amdgcn_update_dpp(x, x, CTRL, 0xf, 0xf, false); }
+template <int CTRL> __device__ __forceinline__ double dss_dpp_mov(double x)
+{
+    return __hiloint2double(dss_dpp_movi<CTRL>(__double2hiint(x)), dss_dpp_movi<CTRL>(__double2loint(x)));
+}
+// broadcast of lane J of every group of eight, J a compile-time constant.  gfx90a+ moves 64 bits per DPP instruction with the
+// row_newbcast controls (lane N of every row of 16 to the whole row); a row holds two groups, told apart by the bank mask
+// (banks 0-1 = lanes 0-7, banks 2-3 = lanes 8-15): two instructions per double.
+template <int J> __device__ __forceinline__ double dss_gbc(double x)
+{
+    const double lo = __builtin_amdgcn_update_dpp(x, x, 0x150 + J, 0xf, 0x3, false);          // lanes 8-15 of the row keep x for now
+    return __builtin_amdgcn_update_dpp(lo, x, 0x150 + 8 + J, 0xf, 0xc, false);
 }
 #endif
 

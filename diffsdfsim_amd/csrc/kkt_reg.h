@@ -10,16 +10,6 @@
 
 namespace dss {
 
-__device__ __forceinline__ double wave_bcast(double x, int src_uniform)
-{
-#if defined(DSS_EMU)
-    return __shfl(x, src_uniform, WAVE);
-#else
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), src_uniform);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), src_uniform);
-    return __hiloint2double(hi, lo);
-#endif
-}
 template <int N> struct RegK {
     double a[N];
 };
@@ -35,13 +25,13 @@ template <int N> __device__ __forceinline__ void regk_factor_natural(RegK<N> &R)
     const int lane = lane_id();
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-        const double inv = 1.0 / wave_bcast(R.a[k], k);
+        const double inv = 1.0 / dss_wave_bcast(R.a[k], k);
         const bool upd = lane > k && lane < N;
         const double l = upd ? R.a[k] * inv : 0.0;
         if (upd) R.a[k] = l;
         if (lane == k) R.a[k] = inv;
 #pragma unroll
-        for (int j = k + 1; j < N; ++j) R.a[j] -= l * wave_bcast(R.a[j], k);
+        for (int j = k + 1; j < N; ++j) R.a[j] -= l * dss_wave_bcast(R.a[j], k);
     }
 }
 template <int N> __device__ __forceinline__ double regk_solve_natural(const RegK<N> &R, double x)
@@ -49,13 +39,13 @@ template <int N> __device__ __forceinline__ double regk_solve_natural(const RegK
     const int lane = lane_id();
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-        const double bk = wave_bcast(x, k);
+        const double bk = dss_wave_bcast(x, k);
         if (lane > k && lane < N) x -= R.a[k] * bk;
     }
     double res = 0.0;
 #pragma unroll
     for (int k = N - 1; k >= 0; --k) {
-        const double xk = wave_bcast(x, k) * wave_bcast(R.a[k], k);
+        const double xk = dss_wave_bcast(x, k) * dss_wave_bcast(R.a[k], k);
         if (lane == k) res = xk;
         if (lane < k) x -= R.a[k] * xk;
     }
@@ -69,13 +59,13 @@ template <int N, int M> __device__ __forceinline__ void regk_factor_lead(RegK<N>
     const int lane = lane_id();
 #pragma unroll
     for (int k = 0; k < M; ++k) {
-        const double inv = 1.0 / wave_bcast(R.a[k], k);
+        const double inv = 1.0 / dss_wave_bcast(R.a[k], k);
         const bool upd = lane > k && lane < M;
         const double l = upd ? R.a[k] * inv : 0.0;
         if (upd) R.a[k] = l;
         if (lane == k) R.a[k] = inv;
 #pragma unroll
-        for (int j = k + 1; j < M; ++j) R.a[j] -= l * wave_bcast(R.a[j], k);
+        for (int j = k + 1; j < M; ++j) R.a[j] -= l * dss_wave_bcast(R.a[j], k);
     }
 }
 // The same for a BLOCK-TRIDIAGONAL leading part (6 x 6 blocks: every contact joins bodies that are neighbours in the body order,
@@ -87,14 +77,14 @@ template <int N, int M> __device__ __forceinline__ void regk_factor_lead_tri(Reg
     const int lane = lane_id();
 #pragma unroll
     for (int k = 0; k < M; ++k) {
-        const double inv = 1.0 / wave_bcast(R.a[k], k);
+        const double inv = 1.0 / dss_wave_bcast(R.a[k], k);
         const bool upd = lane > k && lane < M;
         const double l = upd ? R.a[k] * inv : 0.0;
         if (upd) R.a[k] = l;
         if (lane == k) R.a[k] = inv;
 #pragma unroll
         for (int j = k + 1; j < M; ++j)
-            if (j < 6 * (k / 6 + 2)) R.a[j] -= l * wave_bcast(R.a[j], k);
+            if (j < 6 * (k / 6 + 2)) R.a[j] -= l * dss_wave_bcast(R.a[j], k);
     }
 }
 template <int N, int M> __device__ __forceinline__ double regk_solve_lead(const RegK<N> &R, double x)
@@ -102,13 +92,13 @@ template <int N, int M> __device__ __forceinline__ double regk_solve_lead(const 
     const int lane = lane_id();
 #pragma unroll
     for (int k = 0; k < M; ++k) {
-        const double bk = wave_bcast(x, k);
+        const double bk = dss_wave_bcast(x, k);
         if (lane > k && lane < M) x -= R.a[k] * bk;
     }
     double res = 0.0;
 #pragma unroll
     for (int k = M - 1; k >= 0; --k) {
-        const double xk = wave_bcast(x, k) * wave_bcast(R.a[k], k);
+        const double xk = dss_wave_bcast(x, k) * dss_wave_bcast(R.a[k], k);
         if (lane == k) res = xk;
         if (lane < k) x -= R.a[k] * xk;
     }

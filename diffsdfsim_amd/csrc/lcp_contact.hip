@@ -183,10 +183,8 @@ struct Lds {
 // contacts longer pieces keep the number of lanes that meet at an LDS address down and the 4 x pieces tasks of the assembly within
 // one round of the wavefront (84 contacts in ~14 runs: 0.543 / 0.537 / 0.533 ms per launch for 4 / 6 / 8); with few contacts every
 // lane's chain should be as short as possible (config 2: <= 8 contacts)
-#if !defined(DSS_CHUNK_BIG)
-#define DSS_CHUNK_BIG 8
-#endif
-__device__ inline int chunk_len(int nc) { return nc > 48 ? DSS_CHUNK_BIG : (nc > 24 ? 2 : 1); }
+constexpr int CHUNK_BIG = 8;
+__device__ inline int chunk_len(int nc) { return nc > 48 ? CHUNK_BIG : (nc > 24 ? 2 : 1); }
 // sizes with a register-resident factor/solve: only H = Q + sum P C P^T is assembled in LDS, the equality rows join
 // in registers and the factored rows are parked in the (L2-resident) workspace between the two solves of an iteration
 __host__ __device__ inline bool reg_path(int n) { return n == 54 || n == 18; }

@@ -31,63 +31,30 @@ __device__ __forceinline__ int grp_lane() { return threadIdx.x & (GS - 1); }
 // value of lane `src` of the own group, src a run-time number (the pivot lane of a pivoted elimination): ds_bpermute
 __device__ __forceinline__ double gsh(double x, int src) { return __shfl(x, (threadIdx.x & (WAVE - GS)) | src, WAVE); }
 
-// Cross-lane traffic with COMPILE-TIME partners runs on the DPP path of the vector ALU (a few cycles) instead of through the
-// LDS crossbar (ds_bpermute / ds_swizzle: > 100 cycles each, and the solves are chains of them):
-//   quad_perm for partners inside a quad, row_half_mirror (lane i <-> 7 - i of every 8) to cross between the two quads.
-#if defined(DSS_EMU)
-template <int CTRL> __device__ __forceinline__ double dpp_mov(double x)
-{
-    const int l = threadIdx.x & 63, q = l & ~3, i = l & 3;
-    const int src = CTRL == 0x141 ? (l & ~7) | (7 - (l & 7)) : q | ((CTRL >> (2 * i)) & 3);
-    return __shfl(x, src, WAVE);
-}
-template <int CTRL> __device__ __forceinline__ int dpp_movi(int x)
-{
-    const int l = threadIdx.x & 63, q = l & ~3, i = l & 3;
-    const int src = CTRL == 0x141 ? (l & ~7) | (7 - (l & 7)) : q | ((CTRL >> (2 * i)) & 3);
-    return __shfl(x, src, WAVE);
-}
-#else
-template <int CTRL> __device__ __forceinline__ int dpp_movi(int x) { return __builtin_amdgcn_update_dpp(x, x, CTRL, 0xf, 0xf, false); }
-template <int CTRL> __device__ __forceinline__ double dpp_mov(double x)
-{
-    return __hiloint2double(dpp_movi<CTRL>(__double2hiint(x)), dpp_movi<CTRL>(__double2loint(x)));
-}
-#endif
+// Cross-lane traffic with compile-time partners runs on the DPP path (dss_dpp_mov, dss_gbc in dss_device.h), not through the LDS
+// crossbar: the solves are chains of them.
 constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HALF_MIRROR = 0x141;     // quad_perm [1,0,3,2], [2,3,0,1]; row_half_mirror
 
-// broadcast of lane J of every group of eight, J a compile-time constant.  gfx90a+ moves 64 bits per DPP instruction with the
-// row_newbcast controls (lane N of every row of 16 to the whole row); a row holds two groups, told apart by the bank mask
-// (banks 0-1 = lanes 0-7, banks 2-3 = lanes 8-15): two instructions per double.
-template <int J> __device__ __forceinline__ double gbc(double x)
-{
-#if defined(DSS_EMU)
-    return __shfl(x, (threadIdx.x & (WAVE - GS)) | J, WAVE);
-#else
-    const double lo = __builtin_amdgcn_update_dpp(x, x, 0x150 + J, 0xf, 0x3, false);          // lanes 8-15 of the row keep x for now
-    return __builtin_amdgcn_update_dpp(lo, x, 0x150 + 8 + J, 0xf, 0xc, false);
-#endif
-}
 __device__ __forceinline__ double gsum(double v)
 {
-    v += dpp_mov<DPP_XOR1>(v); v += dpp_mov<DPP_XOR2>(v); v += dpp_mov<DPP_HALF_MIRROR>(v);
+    v += dss_dpp_mov<DPP_XOR1>(v); v += dss_dpp_mov<DPP_XOR2>(v); v += dss_dpp_mov<DPP_HALF_MIRROR>(v);
     return v;
 }
 __device__ __forceinline__ double gmin(double v)
 {
-    v = fmin(v, dpp_mov<DPP_XOR1>(v)); v = fmin(v, dpp_mov<DPP_XOR2>(v)); v = fmin(v, dpp_mov<DPP_HALF_MIRROR>(v));
+    v = fmin(v, dss_dpp_mov<DPP_XOR1>(v)); v = fmin(v, dss_dpp_mov<DPP_XOR2>(v)); v = fmin(v, dss_dpp_mov<DPP_HALF_MIRROR>(v));
     return v;
 }
 __device__ __forceinline__ double gmax(double v)
 {
-    v = fmax(v, dpp_mov<DPP_XOR1>(v)); v = fmax(v, dpp_mov<DPP_XOR2>(v)); v = fmax(v, dpp_mov<DPP_HALF_MIRROR>(v));
+    v = fmax(v, dss_dpp_mov<DPP_XOR1>(v)); v = fmax(v, dss_dpp_mov<DPP_XOR2>(v)); v = fmax(v, dss_dpp_mov<DPP_HALF_MIRROR>(v));
     return v;
 }
 // arg-max over the group, lowest lane on ties (LAPACK idamax)
 template <int CTRL> __device__ __forceinline__ void argmax_step(double &v, int &idx)
 {
-    const double ov = dpp_mov<CTRL>(v);
-    const int oi = dpp_movi<CTRL>(idx);
+    const double ov = dss_dpp_mov<CTRL>(v);
+    const int oi = dss_dpp_movi<CTRL>(idx);
     if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
 }
 
@@ -123,7 +90,7 @@ template <bool PIV, int K> __device__ __forceinline__ void glu_factor_step(GLU &
         for (int j = K; j < GS; ++j) pr[j] = gsh(M.a[j], p);
     } else {
 #pragma unroll
-        for (int j = K; j < GS; ++j) pr[j] = gbc<K>(M.a[j]);
+        for (int j = K; j < GS; ++j) pr[j] = dss_gbc<K>(M.a[j]);
         ok = pr[K] != 0.0;
     }
     if (!ok && !info) info = K + 1;
@@ -157,7 +124,7 @@ template <bool PIV, int K, int NC> __device__ __forceinline__ void glu_fwd_step(
     const bool later = PIV ? (M.ord > K && r < n) : (r > K && r < n);     // rows that come later in the pivot order lose l * (pivot row's b)
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        const double bp = PIV ? gsh(b[c], p) : gbc<K>(b[c]);
+        const double bp = PIV ? gsh(b[c], p) : dss_gbc<K>(b[c]);
         if (later) b[c] -= M.a[K] * bp;
     }
 }
@@ -170,7 +137,7 @@ template <bool PIV, int K, int NC> __device__ __forceinline__ void glu_bwd_step(
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const double mine = b[c] * M.a[K];                  // (meaningful in the pivot lane only: a[K] = 1 / U_KK there)
-        const double xk = PIV ? gsh(mine, p) : gbc<K>(mine);
+        const double xk = PIV ? gsh(mine, p) : dss_gbc<K>(mine);
         if (earlier) b[c] -= M.a[K] * xk;
         if (r == K) x[c] = xk;
     }
@@ -197,7 +164,7 @@ template <bool PIV> __device__ __forceinline__ double glu_solve1(const GLU &M, i
 // y_r = sum_{j < n} m[j] x_j  (row r of a matrix times a vector whose element j lives in lane j)
 template <int J> __device__ __forceinline__ void gmatvec_step(const double (&m)[GS], double x, int n, double &acc)
 {
-    if (J < n) acc += m[J] * gbc<J>(x);
+    if (J < n) acc += m[J] * dss_gbc<J>(x);
 }
 __device__ __forceinline__ double gmatvec(const double (&m)[GS], double x, int n)
 {
@@ -213,7 +180,7 @@ template <int L> __device__ __forceinline__ void gmatmul_step(const double (&a)[
 #pragma unroll
     for (int j = 0; j < GS; ++j) {
         if (j >= ncol) break;
-        c[j] += a[L] * gbc<L>(b[j]);
+        c[j] += a[L] * dss_gbc<L>(b[j]);
     }
 }
 __device__ __forceinline__ void gmatmul(const double (&a)[GS], const double (&b)[GS], int k, int ncol, double (&c)[GS])
@@ -375,7 +342,7 @@ template <int K> __device__ __forceinline__ void spd_step(double (&a)[GS], int n
     const int r = grp_lane();
     double pr[GS];
 #pragma unroll
-    for (int j = K; j < GS; ++j) pr[j] = gbc<K>(a[j]);
+    for (int j = K; j < GS; ++j) pr[j] = dss_gbc<K>(a[j]);
     if (!(pr[K] > 0.0)) ok = 0;
     if (r > K && r < nz) {
         const double l = a[K] / pr[K];
@@ -397,10 +364,9 @@ __device__ __forceinline__ int g_is_spd(const GSys &S, const double *Q, size_t s
     return ok;
 }
 
-#if !defined(DSS_GRP_WAVES)
-#define DSS_GRP_WAVES 2
-#endif
-__global__ void __launch_bounds__(64, DSS_GRP_WAVES)
+// two wavefronts per SIMD: faster than one or three
+constexpr int GRP_WAVES = 2;
+__global__ void __launch_bounds__(64, GRP_WAVES)
 lcp_dense_group_forward_kernel(const double *Q, const double *p, const double *G, const double *h, const double *A, const double *b,
                                const double *F, int B, int nz, int ni, int ne, double eps, int not_improved_lim, int max_iter,
                                int check_spd, double *zhat, double *lam, double *slack, double *nu, int *iters, int *status)
@@ -516,7 +482,7 @@ lcp_dense_group_backward_kernel(const double *Q, const double *G, const double *
     const double lz = on ? lv : 0.0;
 #define DSS_GRP_OUTER(J)                                                                                                 \
     {                                                                                                                    \
-        const double zj = gbc<J>(zl), dxj = gbc<J>(dx), lj = gbc<J>(lz);                                                 \
+        const double zj = dss_gbc<J>(zl), dxj = dss_gbc<J>(dx), lj = dss_gbc<J>(lz);                                     \
         if (w && J < nz) {                                                                                               \
             if (r < nz) dQ[sys * nz * nz + (size_t)r * nz + J] = 0.5 * (dx * zj + zl * dxj);                              \
             if (on) dG[sys * ni * nz + (size_t)r * nz + J] = dlam * zj + lv * dxj;                                        \

@@ -30,11 +30,8 @@
 
 #include "np_common.h"
 
-#ifndef DSS_NP_WAVES
-#define DSS_NP_WAVES 3   // waves per SIMD the register allocator must leave room for (= workgroups per CU)
-#endif
-
 namespace {
+constexpr int NP_WAVES = 3;   // waves per SIMD the register allocator must leave room for (= workgroups per CU)
 // ---- _overlap ---------------------------------------------------------------------------------
 // "Does any vertex of one body lie in the other's query cube", both ways, for every undirected pair.  One workgroup
 // per scene, its four wavefronts take the pairs round robin (no barrier inside a pair: the work per pair is a short
@@ -51,7 +48,7 @@ __global__ void __launch_bounds__(OV_NT) overlap_kernel(DssWorld W)
     if (!W.active[sc]) return;
     // (a batch with fewer items than the grid has workgroups -- the time of the launch is then the latency of its longest item:
     // the items that search a big mesh get a whole workgroup, whose four wavefronts scan it a quarter each)
-    const bool few = (long)W.B * np <= 256L * DSS_NP_WAVES;
+    const bool few = (long)W.B * np <= 256L * NP_WAVES;
     if (tid < nb) {
         const int nf = W.mesh_nf[W.mesh_id[(size_t)sc * nb + tid]];
         s_big[tid] = nf > WAVE_ITEM_MAX_FACES || (few && nf > 2048);
@@ -627,7 +624,7 @@ union NpScratch {
     ScratchT<BlockGroup> blk;
     ScratchT<WaveGroup> wav[BlockGroup::NW];
 };
-template <bool DEFERRED> __global__ void __launch_bounds__(NT, DSS_NP_WAVES) narrowphase_kernel(DssWorld W_arg)
+template <bool DEFERRED> __global__ void __launch_bounds__(NT, NP_WAVES) narrowphase_kernel(DssWorld W_arg)
 {
     DSS_KERNARG_REF(DssWorld, W, W_arg);
     __shared__ NpScratch S;
@@ -728,11 +725,11 @@ __global__ void __launch_bounds__(64) compact_contacts_kernel(DssWorld W, int *n
 }  // namespace
 
 namespace dss {
-// 256 CUs x DSS_NP_WAVES resident workgroups walk the work lists; every wavefront of the grid owns one scratch slot
+// 256 CUs x NP_WAVES resident workgroups walk the work lists; every wavefront of the grid owns one scratch slot
 static inline int np_grid(int B, int nb)
 {
     const long items = (long)B * nb * (nb - 1);
-    return (int)(items < 256 * DSS_NP_WAVES ? items : 256 * DSS_NP_WAVES);
+    return (int)(items < 256 * NP_WAVES ? items : 256 * NP_WAVES);
 }
 // enqueue detection at the current pose; results land in (nc_out, body_out, ...)
 #if DSS_ALL_SHAPES
@@ -757,7 +754,7 @@ int launch_find_contacts(const DssWorld &W, int *nc_out, int *body_out, int *fac
     const int nup = W.nb * (W.nb - 1) / 2, np = W.nb * (W.nb - 1);
     (void)hipMemsetAsync(W.n_pairs, 0, 8 * sizeof(int), stream);   // counts and cursors of the work lists
     hipLaunchKernelGGL(overlap_kernel, dim3(W.B), dim3(OV_NT), 0, stream, W);
-    // 256 CUs x DSS_NP_WAVES resident workgroups walk the work lists; no idle dispatches
+    // 256 CUs x NP_WAVES resident workgroups walk the work lists; no idle dispatches
     const int grid = np_grid(W.B, W.nb);
     hipLaunchKernelGGL(narrowphase_kernel<false>, dim3(grid), dim3(NT), 0, stream, W);
     // normally finds an empty list: a small grid keeps the empty launch cheap, and works a real list off all the same

@@ -10,10 +10,6 @@
 #include "contact_geom.h"
 #include "wave_utils.h"
 
-// 3-D hull of a contact cluster with Qhull's vertex semantics (coincident points are one vertex, points in a triangle of
-// others are none).  Needed by every variant: neighbouring faces of an icosphere converge to shared vertices too.
-#define DSS_HULL_EXACT 1
-
 namespace {
 using namespace dss;
 
@@ -121,11 +117,7 @@ template <int BT_, int HCAP_, int CHCAP_> struct Group {
     __device__ static inline int any(int x) { if (BT_ == 64) return __ballot(x) != 0ull; else return __syncthreads_or(x); }
 };
 using BlockGroup = Group<256, 1024, 704>;
-#if defined(DSS_NP_EXP_HCAP)
-using WaveGroup = Group<64, DSS_NP_EXP_HCAP, 32>;
-#else
 using WaveGroup = Group<64, 384, 32>;
-#endif
 
 template <class G> struct ScratchT {
     int wave_tot[G::NW];
@@ -156,16 +148,6 @@ template <class G> __device__ inline int compact_slot(int flag, int &count, Scra
 }
 
 // block arg-min over (key, index) with lowest index on ties; returns the index (or -1 if none valid)
-// value of lane 0, for every lane (the xor butterfly leaves the same set summed in every lane, but only lane 0's
-// order of additions is that of the LDS tree the workgroup flavour uses)
-__device__ inline double wave_first(double x)
-{
-#if defined(DSS_EMU)
-    return __shfl(x, 0, 64);
-#else
-    return dss_uniform(x);
-#endif
-}
 template <class G> __device__ inline int block_argmin(double key, int idx, ScratchT<G> &S)
 {
     if (G::BT == 64) {   // one wavefront: shuffles, no LDS round trips; (key, index) minimum is order independent
@@ -203,9 +185,11 @@ template <class G> __device__ inline double block_max(double v, ScratchT<G> &S)
     G::sync();
     return r;
 }
+// (wavefront: the xor butterfly leaves the same set summed in every lane, but only lane 0's order of additions is that of
+// the LDS tree the workgroup flavour uses)
 template <class G> __device__ inline double block_sum(double v, ScratchT<G> &S)
 {
-    if (G::BT == 64) return wave_first(wave_sum(v));   // same association as the tree below, bit for bit
+    if (G::BT == 64) return dss_wave_first(wave_sum(v));   // same association as the tree below, bit for bit
     const int tid = G::tid();
     S.red_d[tid] = v;
     G::sync();
@@ -450,6 +434,8 @@ template <class G, class P_> __device__ bool hull3_wrap(ScratchT<G> &S, const P_
 }
 #endif
 
+// The 3-D hull has Qhull's vertex semantics (coincident points are one vertex, points in a triangle of others are none), in
+// every variant: neighbouring faces of an icosphere converge to shared vertices too.
 // Returns 2 (lean variant) if the cluster has more than 48 distinct non-coplanar points -- every one of them is kept and the
 // caller flags the scene; 1 if a wavefront-sized group has to hand the item to a workgroup (full variant: a cluster of more than 48 distinct
 // non-coplanar points gets the gift-wrapped hull, which keeps its edge list in the workgroup's LDS), else 0.
@@ -524,7 +510,6 @@ template <class G, class P_> __device__ int cluster_hull(ScratchT<G> &S, P_ P, i
             }
         }
     }
-#if DSS_HULL_EXACT
 #if DSS_ALL_SHAPES
     // workgroup flavour, more points than the pairwise duplicate search below is meant for: gift wrapping
     if (!flat3 && G::BT != 64 && m > 2048) {
@@ -628,19 +613,6 @@ template <class G, class P_> __device__ int cluster_hull(ScratchT<G> &S, P_ P, i
             const int iu = e / (mu * mu), ju = (e / mu) % mu, ku = e % mu;
             if (!(iu < ju && ju < ku)) continue;
             const int i = S.red_i[iu], j = S.red_i[ju], k = S.red_i[ku];
-#else
-    if (!flat3) {
-        if (m > HULL3_MAX) {  // beyond the brute-force limit: keep every point (superset of the hull)
-            for (int k = tid; k < m; k += G::BT) P.setf(k, 1);
-            G::sync();
-            return 0;
-        }
-        // supporting-plane test over all triples
-        const int ntri = m * m * m;
-        for (int e = tid; e < ntri; e += G::BT) {
-            const int i = e / (m * m), j = (e / m) % m, k = e % m;
-            if (!(i < j && j < k)) continue;
-#endif
             const double u[3] = {P.hp(j, 0) - P.hp(i, 0), P.hp(j, 1) - P.hp(i, 1), P.hp(j, 2) - P.hp(i, 2)};
             const double v[3] = {P.hp(k, 0) - P.hp(i, 0), P.hp(k, 1) - P.hp(i, 1), P.hp(k, 2) - P.hp(i, 2)};
             double n[3];
@@ -652,7 +624,6 @@ template <class G, class P_> __device__ int cluster_hull(ScratchT<G> &S, P_ P, i
                 const double sd = (n[0] * (P.hp(q, 0) - P.hp(i, 0)) + n[1] * (P.hp(q, 1) - P.hp(i, 1)) + n[2] * (P.hp(q, 2) - P.hp(i, 2))) / ln;
                 pos |= sd > tolf; neg |= sd < -tolf;
             }
-#if DSS_HULL_EXACT
             for (int qu = 0; qu < mu; ++qu) {
                 const int q = S.red_i[qu];
                 if (q == i || q == j || q == k) continue;
@@ -666,15 +637,12 @@ template <class G, class P_> __device__ int cluster_hull(ScratchT<G> &S, P_ P, i
                 const double bk = (c2[0] * n[0] + c2[1] * n[1] + c2[2] * n[2]) / (ln * ln);
                 if (bj >= -1e-9 && bk >= -1e-9 && 1.0 - bj - bk >= -1e-9) S.red_d[qu] = 1.0;
             }
-#endif
             if (!(pos && neg)) { P.setf(i, 1); P.setf(j, 1); P.setf(k, 1); }
         }
         G::sync();
-#if DSS_HULL_EXACT
         for (int k = tid; k < m; k += G::BT) if (P.getf(k) == 3) P.setf(k, 0);
         for (int qu = tid; qu < mu; qu += G::BT) if (S.red_d[qu] != 0.0) P.setf(S.red_i[qu], 0);
         G::sync();
-#endif
         return 0;
     }
     // ---- 2-D: drop the coordinate of least variance (first index on ties, torch.argmin) ---------

@@ -128,8 +128,9 @@ class BatchEngine:
                 j = int(np.nonzero(mid == m)[0][0])
                 vg.append(default_vgrad(int(st[j]), sp[j], verts))
         mt = mesh_table(spec["meshes"], vg)
-        shapes = abi.array_shapes(B, nb, neq, maxc, fric_dirs, max_cand, max_pc, max_sub, len(spec["meshes"]),
-                                  len(mt["verts"]), len(mt["faces"]), len(mt["fch_box"]), len(mt["vch_box"]))
+        L = self.be.lib
+        shapes = abi.array_shapes(B, nb, neq, maxc, fric_dirs, max_cand, max_pc, max_sub, len(spec["meshes"]), len(mt["verts"]),
+                                  len(mt["faces"]), L.dss_np_slots(int(B), int(nb)), len(mt["fch_box"]), len(mt["vch_box"]))
         # neural SDF bodies (shape_type 6): network weights + the scratch of the round-based narrow phase
         st_all = np.asarray(spec["shape_type"]).reshape(B, nb)
         igr_b = st_all == abi.SHAPE_IGR
@@ -193,19 +194,15 @@ class BatchEngine:
                 setattr(W, name, self.be.ptr(self.arr[name]) if name in self.arr else None)
         # neural narrow phase: what the previous detection found (host side), which sizes the grids of the next one
         self.igr_hint = None
-        import os
-        if self.igr_items_cap > 0 and not os.environ.get("DSS_NO_IGR_HINT"):
+        if self.igr_items_cap > 0:
             self.igr_hint = np.full(2 * (abi.IGR_ROUNDS + 2), -1, np.int32)
             self.igr_hint[0] = self.igr_items_cap
             W.igr_hint = self.igr_hint.ctypes.data
         self.W = W
-        L = self.be.lib
         L.dss_world_sizeof.restype = ctypes.c_size_t
         if L.dss_world_sizeof() != ctypes.sizeof(abi.DssWorld):
             raise RuntimeError("DssWorld layout mismatch: library %d bytes, python mirror %d bytes"
                                % (L.dss_world_sizeof(), ctypes.sizeof(abi.DssWorld)))
-        if L.dss_np_slots(int(B), int(nb)) != abi.np_slots(int(B), int(nb)):
-            raise RuntimeError("narrow-phase slot count mismatch between the library and its python mirror")
         L.dss_lcp_contact_workspace_bytes.restype = ctypes.c_size_t
         nbytes = L.dss_lcp_contact_workspace_bytes(B, nb, neq, maxc, fric_dirs)
         self.lcp_ws = self.be.zeros((nbytes,), np.uint8)

@@ -4,7 +4,6 @@ The field order below IS the struct layout; ``dss_world_sizeof()`` is checked ag
 world is first bound to the library, so a mismatch fails loudly instead of corrupting memory.
 """
 import ctypes
-import os
 
 import numpy as np
 
@@ -59,11 +58,6 @@ class DssWorld(ctypes.Structure):
 NP_DTYPE = {"pd": np.float64, "pi": np.int32, "pb": np.uint8}
 
 
-def np_slots(B, nb):
-    """Scratch slots of the persistent narrow phase = wavefronts of its grid (mirrors dss_np_slots)."""
-    return 4 * min(B * nb * (nb - 1), 256 * int(os.environ.get("DSS_NP_WAVES", 3)))     # (env: kernel experiments only)
-
-
 def igr_shapes(items_cap, qcap, max_cand):
     """Arrays of the round-based narrow phase for neural SDF bodies (narrowphase_igr.hip)."""
     return {
@@ -74,8 +68,8 @@ def igr_shapes(items_cap, qcap, max_cand):
     }
 
 
-def array_shapes(B, nb, neq, maxc, fd, max_cand, max_pc, max_sub, nmesh, NV, NF, NFC=1, NVC=1):
-    """Shapes of every array the kernels touch (state, scratch, tape)."""
+def array_shapes(B, nb, neq, maxc, fd, max_cand, max_pc, max_sub, nmesh, NV, NF, np_slots, NFC=1, NVC=1):
+    """Shapes of every array the kernels touch (state, scratch, tape); np_slots = dss_np_slots(B, nb)."""
     npair = nb * (nb - 1)
     NR = fd + 2
     NFc = 3 * (1 + fd // 2) + 8
@@ -97,8 +91,7 @@ def array_shapes(B, nb, neq, maxc, fd, max_cand, max_pc, max_sub, nmesh, NV, NF,
         "ovl": (B, nb, nb), "pair_list": (3 * B * npair,), "n_pairs": (8,), "invalid": (B,), "overflow": (B,),
         "pc_count": (B, npair), "pc_stats": (B, npair, 2), "pc_face": (B, npair, max_pc), "pc_abc": (B, npair, 3, max_pc),
         "pc_geom": (B, npair, 10, max_pc),
-        "cand_face": (np_slots(B, nb), 2, max_cand), "cand_state": (np_slots(B, nb), max_cand),
-        "cand_buf": (np_slots(B, nb), CAND_FIELDS, max_cand),
+        "cand_face": (np_slots, 2, max_cand), "cand_state": (np_slots, max_cand), "cand_buf": (np_slots, CAND_FIELDS, max_cand),
     }
     if max_sub > 0:
         s.update({

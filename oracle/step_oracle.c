@@ -356,7 +356,6 @@ static int filter_contacts(world_t *W, const contact_t *c, int n, int *keep)
         while (dim > 1) {
             for (int i = 0; i < m; ++i) for (int k = 0; k < dim; ++k) pr[dim * i + k] = ps[3 * i + cols[k]];
             nh = W->hull_cb ? W->hull_cb(pr, m, dim, ho) : own_hull(pr, m, dim, ho);
-            if (getenv("SO_DEBUG_HULL")) { fprintf(stderr, "hull dim %d m %d -> %d:", dim, m, nh); for (int i = 0; i < m; ++i) { fprintf(stderr, " ("); for (int k = 0; k < dim; ++k) fprintf(stderr, "%.17g,", pr[dim * i + k]); fprintf(stderr, ")"); } fprintf(stderr, "\n"); }
             if (nh == -2) { W->err = 3; nh = 0; break; }
             if (nh >= 0) break;
             /* QhullError: drop the dimension of smallest (unbiased) variance; with one point every variance is NaN and
@@ -501,7 +500,6 @@ static int search_contacts(world_t *W, int i1, int i2)
         double s1 = query(b1, xb1, g1);
         qapply(q12, g1, r);
         double xx[3] = {x[3 * c] - s1 * r[0], x[3 * c + 1] - s1 * r[1], x[3 * c + 2] - s1 * r[2]};
-        if (getenv("SO_DEBUG")) fprintf(stderr, "fw %d->%d face %d abc %.17g %.17g %.17g sdf %.17g\n", i1, i2, cf[c], abc[3 * c], abc[3 * c + 1], abc[3 * c + 2], query(b2, xx, NULL));
         if (query(b2, xx, NULL) <= eps) {
             contact_t ct; memset(&ct, 0, sizeof ct);
             compute_contact(b1, b2, cf[c], abc + 3 * c, &ct);

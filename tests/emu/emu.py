@@ -27,7 +27,8 @@ def _c(a, dtype=np.float64):
     return np.ascontiguousarray(np.asarray(a, dtype=dtype))
 
 
-def lcp_dense_forward(Q, p, G, h, A, b, F, eps=1e-12, nil=3, max_iter=20, check_spd=True):
+def lcp_dense_forward(Q, p, G, h, A, b, F, eps=1e-12, nil=3, max_iter=20, check_spd=True, wave=False):
+    """wave=True: the wavefront-per-system kernel whatever the size (test hook lcp_dense_wave.cpp)."""
     L = lib()
     Q, p, G, h, A, b, F = (_c(x) for x in (Q, p, G, h, A, b, F))
     B, nineq, nz = G.shape
@@ -36,9 +37,10 @@ def lcp_dense_forward(Q, p, G, h, A, b, F, eps=1e-12, nil=3, max_iter=20, check_
     iters = np.zeros(B, np.int32); status = np.zeros(B, np.int32)
     nbytes = L.dss_lcp_dense_workspace_bytes(B, nz, nineq, neq)
     ws = np.zeros(nbytes, np.uint8)
-    rc = L.dss_lcp_dense_forward(_p(Q), _p(p), _p(G), _p(h), _p(A), _p(b), _p(F), B, nz, nineq, neq,
-                                 ctypes.c_double(eps), nil, max_iter, int(check_spd), _p(zhat), _p(lam), _p(slack),
-                                 _p(nu), _p(iters), _p(status), _p(ws), ctypes.c_size_t(nbytes), None)
+    fn = L.dss_emu_lcp_dense_wave_forward if wave else L.dss_lcp_dense_forward
+    rc = fn(_p(Q), _p(p), _p(G), _p(h), _p(A), _p(b), _p(F), B, nz, nineq, neq,
+            ctypes.c_double(eps), nil, max_iter, int(check_spd), _p(zhat), _p(lam), _p(slack),
+            _p(nu), _p(iters), _p(status), _p(ws), ctypes.c_size_t(nbytes), None)
     assert rc == 0, rc
     return zhat, lam, slack, nu, iters, status
 

@@ -42,14 +42,13 @@ def test_emulated_kernel_on_config1_calls():
 
 
 @pytest.mark.parametrize("nB,nz,nineq,neq", [(11, 6, 4, 3), (9, 6, 8, 3), (10, 3, 4, 0), (8, 8, 8, 5), (5, 7, 5, 2)])
-def test_eight_lanes_per_system_kernel_matches_oracle_and_the_wave_kernel(nB, nz, nineq, neq, monkeypatch):
+def test_eight_lanes_per_system_kernel_matches_oracle_and_the_wave_kernel(nB, nz, nineq, neq):
     """csrc/lcp_dense_group.hip (nz, nineq, neq <= 8: eight systems per wavefront, matrices row-distributed in registers) against
     the C oracle on random systems -- batch sizes that are not a multiple of eight (padding groups), several groups with different
     iteration counts in one wavefront, no equalities, full 8 x 8 tiles -- forward (iterates, iteration counts, status) and the
-    implicit backward; and against the wave-per-system kernel it replaces for these sizes (DSS_LCP_DENSE_WAVE=1)."""
+    implicit backward; and against the wave-per-system kernel it replaces for these sizes (through the emulator's test hook)."""
     from oracle import lcp_oracle as O
     Q, p, G, h, A, b, F = random_lcp(11 + nz + nineq, nB, nz, nineq, neq)
-    monkeypatch.delenv("DSS_LCP_DENSE_WAVE", raising=False)
     z, lam, s, nu, it, st = emu.lcp_dense_forward(Q, p, G, h, A, b, F)
     zo, lo, so, nuo, ito, sto = O.forward(Q, p, G, h, A, b, F)
     assert (st == sto).all() and (it == ito).all(), (it, ito)
@@ -60,6 +59,5 @@ def test_eight_lanes_per_system_kernel_matches_oracle_and_the_wave_kernel(nB, nz
     for name, got, want in zip("QpGhAbF", out, ref):
         if want.size:
             assert rel(got, want) < 1e-8, name
-    monkeypatch.setenv("DSS_LCP_DENSE_WAVE", "1")
-    zw, lw, sw, nuw, itw, stw = emu.lcp_dense_forward(Q, p, G, h, A, b, F)
+    zw, lw, sw, nuw, itw, stw = emu.lcp_dense_forward(Q, p, G, h, A, b, F, wave=True)
     assert (itw == it).all() and rel(zw, z) < 1e-9
