@@ -14,9 +14,10 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libdiffsdfsim_hip.so")
+DIAG_LIB_PATH = os.path.join(CSRC, "libdiffsdfsim_hip_diag.so")
 _LIB = None
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 
 class HipLibraryError(RuntimeError):
@@ -44,14 +45,18 @@ def file_flags(name):
     return _DEFAULT_LLVM.get(name, _NO_LSR) + PER_FILE_FLAGS.get(name, [])
 
 
-def build(force=False, verbose=False):
+def build(force=False, verbose=False, diag=False):
     """hipcc --offload-arch=gfx950: every csrc/*.hip -> csrc/_obj/*.o (rebuilt when it or a header is newer),
-    linked into csrc/libdiffsdfsim_hip.so."""
+    linked into csrc/libdiffsdfsim_hip.so.  diag=True: the same sources with the same flags plus -DDSS_DIAG (the phase time
+    stamps of diag_stamps.h and the micro-benchmarks of diag_latency.hip; tools/*_phases.py, tools/latency.py) ->
+    csrc/_obj_diag/*.o, csrc/libdiffsdfsim_hip_diag.so.  Returns the library's path."""
     srcs = sources()
-    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(_HERE, "..", "include", "*.h"))
+    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + \
+        glob.glob(os.path.join(_HERE, "..", "include", "*.h"))
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    extra = os.environ.get("DSS_HIPCC_FLAGS", "").split()
-    objdir = os.path.join(CSRC, "_obj")
+    extra = os.environ.get("DSS_HIPCC_FLAGS", "").split() + (["-DDSS_DIAG"] if diag else [])
+    objdir = os.path.join(CSRC, "_obj_diag" if diag else "_obj")
+    lib_path = DIAG_LIB_PATH if diag else LIB_PATH
     os.makedirs(objdir, exist_ok=True)
     stamp = os.path.join(objdir, "flags.txt")
     flagsig = " ".join(extra) + repr(sorted(PER_FILE_FLAGS.items())) + repr(_NO_LSR) + repr(sorted(_DEFAULT_LLVM.items())) + "cuid=stem"
@@ -78,14 +83,14 @@ def build(force=False, verbose=False):
     for cmd, pr in procs:
         if pr.wait() != 0:
             raise subprocess.CalledProcessError(pr.returncode, cmd)
-    if procs or not os.path.exists(LIB_PATH) or any(os.path.getmtime(o) > os.path.getmtime(LIB_PATH) for o in objs):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
+    if procs or not os.path.exists(lib_path) or any(os.path.getmtime(o) > os.path.getmtime(lib_path) for o in objs):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path] + objs
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
     with open(stamp, "w") as f:
         f.write(flagsig)
-    return LIB_PATH
+    return lib_path
 
 
 def lib():

@@ -35,14 +35,9 @@
 #include "kkt_reg.h"
 #include "wave_utils.h"
 
-#if defined(DSS_DIAG)   // diagnostic build only (tools/lcp_phases.py); the product library has no global state
-__device__ long long *g_lcp_stamps = nullptr;
-#define LSTAMP(i) do { if (g_lcp_stamps && threadIdx.x == 0) atomicAdd((unsigned long long *)&g_lcp_stamps[(size_t)blockIdx.x * 16 + (i)], (unsigned long long)(wall_clock64() - t_last)); t_last = wall_clock64(); } while (0)
-#define LSTAMP_INIT long long t_last = wall_clock64()
-#else
-#define LSTAMP(i) do { } while (0)
-#define LSTAMP_INIT do { } while (0)
-#endif
+#define DSS_STAMPS lcp   // phase times of the forward kernel in the diagnostic build (tools/lcp_phases.py)
+#include "diag_stamps.h"
+#define LSTAMP(i) DSS_STAMP_ADD(threadIdx.x == 0, (size_t)blockIdx.x * 16 + (i))
 
 namespace {
 using namespace dss;
@@ -719,7 +714,7 @@ lcp_contact_forward_kernel(const double *Mblk_, const double *pvec_, const doubl
 
     int it = 0, not_improved = 0, have_best = 0;
     double best = 0.0;
-    LSTAMP_INIT;
+    DSS_STAMP_INIT;
     LSTAMP(0);
     for (it = 0; it < max_iter; ++it) {
         // ---- residuals (batch.py:117-131), the affine right-hand side and K(d) ------------------
@@ -1126,14 +1121,6 @@ inline bool dims_ok(int B, int nb, int neq, int maxc, int fd)
 }
 
 }  // namespace
-
-#if defined(DSS_DIAG)
-__global__ void set_lcp_stamps_kernel(long long *p) { g_lcp_stamps = p; }
-extern "C" void dss_diag_set_lcp_stamps(long long *p, void *stream)
-{
-    hipLaunchKernelGGL(set_lcp_stamps_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, p);
-}
-#endif
 
 extern "C" {
 

@@ -26,6 +26,9 @@
 #ifndef DSS_ALL_SHAPES
 #define DSS_ALL_SHAPES 0
 #endif
+#if !DSS_ALL_SHAPES
+#define DSS_STAMPS np    // phase times of the lean kernel's work items in the diagnostic build (tools/np_phases.py)
+#endif
 
 
 #include "np_common.h"
@@ -154,7 +157,6 @@ __global__ void __launch_bounds__(OV_NT) overlap_kernel(DssWorld W)
 // ---- the narrow phase -------------------------------------------------------------------------
 template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S, int item, int slot_id)
 {
-#define STAMP(i) do { if (W.dbg_stamps && G::tid() == 0) W.dbg_stamps[(size_t)item * 8 + (i)] = wall_clock64(); } while (0)
     STAMP(0);
     item = dss_uniform(item); slot_id = dss_uniform(slot_id);
     const int np = npairs_of(W.nb);
@@ -611,7 +613,6 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
 #define NP_PRESTATE 1
 #include "np_filter_emit.inc"
 #undef NP_PRESTATE
-#undef STAMP
 #undef CB
 }
 

@@ -8,6 +8,7 @@
 
 #include "../../include/diffsdfsim_hip.h"
 #include "contact_geom.h"
+#include "diag_stamps.h"
 #include "wave_utils.h"
 
 namespace {
@@ -20,6 +21,8 @@ constexpr int HULL3_MAX = 48;    // brute-force 3-D hull size limit
 // floor are 688 tests (11 rounds of 64 lanes), after which the item is as small as any other, and a workgroup item keeps
 // four wavefronts busy for what is mostly a serial chain.  Items that outgrow the wavefront's scratch are deferred.
 constexpr int WAVE_ITEM_MAX_FACES = 1 << 30;
+// time stamp i of a work item, [item][8] (diag_stamps.h: the lean narrow phase of the diagnostic build; nothing elsewhere)
+#define STAMP(i) DSS_STAMP(G::tid() == 0, (size_t)item * 8 + (i))
 
 __device__ inline int npairs_of(int nb) { return nb * (nb - 1); }
 __device__ inline void pair_of(int dp, int nb, int &a, int &b)
@@ -779,7 +782,6 @@ __device__ __noinline__ void emit_unfiltered(const DssWorld &W, int sc, int dp, 
 // contacts k < ncon: kface[k], barycentrics (fields 15-17), normal (18-20), p1 (21-23), p2 (0-2), penetration (24).
 // Returns 1 if a wavefront-sized group has to hand the item to a workgroup, else 0.
 #define CB(f, k) cb[(size_t)(f) * MC + (k)]
-#define STAMP(i) do { if (W.dbg_stamps && G::tid() == 0) W.dbg_stamps[(size_t)item * 8 + (i)] = wall_clock64(); } while (0)
 template <class G>
 __device__ __forceinline__ int filter_and_emit(const DssWorld &W, ScratchT<G> &S, int item, int sc, int dp, int ncon, int over,
                                                int *__restrict__ cface, int *__restrict__ kface, int *__restrict__ cstate,
@@ -789,7 +791,6 @@ __device__ __forceinline__ int filter_and_emit(const DssWorld &W, ScratchT<G> &S
     int *pc_count = W.pc_count + (size_t)sc * np + dp;
 #include "np_filter_emit.inc"
 }
-#undef STAMP
 #undef CB
 
 }  // namespace

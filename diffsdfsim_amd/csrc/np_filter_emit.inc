@@ -2,7 +2,7 @@
 // of each; contacts.py:97-158) and write the kept ones, in ascending face order, to the pair's output slots.
 // Included inside narrow_pair (narrowphase.hip; the lean kernel's register allocation depends on this code sitting in that
 // function as written) and as the body of filter_and_emit (np_common.h) for the round-based neural narrow phase.
-// Expects in scope: G, W, S, item, sc, np, dp, tid, ncon, over, cface, kface, cstate, cb + CB(f, k), MC, pc_count, STAMP(i).
+// Expects in scope: G, W, S, item, sc, np, dp, tid, ncon, over, cface, kface, cstate, cb + CB(f, k), MC, pc_count, STAMP(i) (np_common.h).
 // On entry the candidate scratch holds, for contacts k < ncon: kface[k], barycentrics (fields 15-17), normal (18-20),
 // p1 (21-23), p2 (0-2), penetration (24).
     STAMP(4);

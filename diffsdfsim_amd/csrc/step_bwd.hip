@@ -105,7 +105,7 @@ template <class T> __device__ inline void attach_grid(const DssWorld &W, int sc,
 // body's normal the contact used, decided by the caller (for neural bodies the Laplacian probes are not repeated).
 // Forward mode (five dual-number passes): the full variant (every primitive, neural / grid bodies, mesh-vertex adjoints).  The
 // lean variant -- box / sphere / cylinder, what the benchmark configs run -- uses the reverse-mode adjoint of contact_rev.h.
-#if DSS_ALL_SHAPES || defined(DSS_BWD_FORWARD_MODE)
+#if DSS_ALL_SHAPES
 __device__ void contact_vjp(const DssWorld &W, int sc, const double *pose_n, int b1, int b2, int face,
                             const double *abc, const double *gbar, double *out, double *g_verts,
                             const double *lin1 = nullptr, const double *lin2 = nullptr, int stable_in = -1)
@@ -531,7 +531,7 @@ __global__ void __launch_bounds__(64) bwd_pre_kernel(DssWorld W_arg, DssAdjoint 
 #endif
         // the forward pass's normal choice travels with the face id: the Laplacian probes are not repeated
         if (st < 0) st = (v.face_n[c] & DSS_FACE_NORMAL1) ? 0 : 1;
-#if DSS_ALL_SHAPES || defined(DSS_BWD_FORWARD_MODE)
+#if DSS_ALL_SHAPES
         contact_vjp(W, sc, v.pose_n, v.body_n[c], v.body_n[MX + c], DSS_FACE_ID(v.face_n[c]), abc, gb, out, A.g_verts, l1, l2, st);
 #else
         {   // reverse mode (contact_rev.h): one value pass, one adjoint pass

@@ -1,7 +1,8 @@
 """ctypes mirror of ``DssWorld`` (include/diffsdfsim_hip.h, section B3) and array allocation.
 
 The field order below IS the struct layout; ``dss_world_sizeof()`` is checked against it when the
-world is first bound to the library, so a mismatch fails loudly instead of corrupting memory.
+world is first bound to the library, so a mismatch fails loudly instead of corrupting memory, and
+tests/test_abi.py checks the names and their order against the header's declarations.
 """
 import ctypes
 
@@ -40,7 +41,7 @@ FIELDS = [
     ("tp_pose", "pd"), ("tp_vel", "pd"), ("tp_dt", "pd"), ("tp_x", "pd"), ("tp_lam", "pd"), ("tp_slack", "pd"),
     ("tp_nu", "pd"), ("tp_abc", "pd"), ("tp_geom", "pd"),
     ("tp_nc", "pi"), ("tp_body", "pi"), ("tp_face", "pi"), ("tp_flags", "pi"), ("tp_t", "pd"),
-    ("ev_lcp_start", "ev"), ("ev_lcp_stop", "ev"), ("ev_np_start", "ev"), ("ev_np_stop", "ev"), ("dbg_stamps", "ev"),
+    ("ev_lcp_start", "ev"), ("ev_lcp_stop", "ev"), ("ev_np_start", "ev"), ("ev_np_stop", "ev"),
     # neural SDF bodies: DssIgrNet (six pointers), capacities, the round-based narrow phase's item state and query lists
     ("igr_W0", "pd"), ("igr_b0", "pd"), ("igr_Wp", "pd"), ("igr_bh", "pd"), ("igr_W8", "pd"), ("igr_b8", "pd"),
     ("igr_items_cap", "i"), ("igr_qcap", "i"), ("igr_rounds", "i"),

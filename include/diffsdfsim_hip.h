@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DSS_ABI_VERSION 1
+#define DSS_ABI_VERSION 2
 
 /* return codes of the launchers */
 #define DSS_OK 0
@@ -213,8 +213,6 @@ typedef struct DssWorld {
     /* optional hipEvent_t pair recorded around the LCP launch of dss_step_attempt (bench roofline) */
     void *ev_lcp_start, *ev_lcp_stop;
     void *ev_np_start, *ev_np_stop;   /* same, around the contact-detection launches */
-    /* optional [grid of narrowphase][8] phase time stamps (diagnostic runs only; NULL in production) */
-    long long *dbg_stamps;
     /* ---- neural SDF bodies (shape_type DSS_SHAPE_IGR; SDF3D(sdf_func=decode_igr(net), params=[latent]), bodies.py:627-760):
        shape_prm[0..1] = the body's latent code, shape_aux = its scale.  A directed pair with a neural body is a work item of
        the round-based narrow phase (narrowphase_igr.hip): items advance from one batch of SDF queries to the next, the
@@ -261,9 +259,9 @@ typedef struct DssWorld {
 #define DSS_IGR_HDR 16         /* ints of per-item state of the round-based narrow phase */
 #define DSS_IGR_ROUNDS 42      /* query rounds that cover every stage: candidates 2, Frank-Wolfe 1 + 31, projection 2, geometry 4, spare */
 
-size_t dss_world_sizeof(void);
+size_t dss_world_sizeof(void);   /* sizeof(DssWorld): lets a binding check its mirror struct */
 /* scratch slots the narrow phase needs for a batch of B scenes with nb bodies (sizes cand_face/cand_state/cand_buf) */
-int dss_np_slots(int B, int nb);   /* sizeof(DssWorld): lets a binding check its mirror struct */
+int dss_np_slots(int B, int nb);
 
 /* Start an outer step of length W->dt for every scene: t_end = t + dt, active = 1 (world.py:119-134). */
 int dss_step_begin(const DssWorld *W, void *stream);

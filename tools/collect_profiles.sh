@@ -4,7 +4,7 @@
 #   part 2: kernel stats of configs 2 and 5, bench line of config 5, dense-LCP HBM table with counters
 #   part 3: counters + kernel stats + bench line of config 4
 # Usage: tools/collect_profiles.sh <part>
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp
 mkdir -p profiles
 bench() { timeout -k 10 900 python3 bench.py --full --config $1 > profiles/r3_bench_config$1.json 2> $TMPDIR/r3_bench_config$1.err || echo "config $1 failed"; cut -c1-260 profiles/r3_bench_config$1.json; }
 kstats() {   # config, steps, extra args

@@ -1,13 +1,10 @@
-"""Dev aid: raw dependent-issue latencies of gfx950 for one wavefront per SIMD (needs the -DDSS_DIAG build)."""
+"""Dev aid: raw dependent-issue latencies of gfx950 for one wavefront per SIMD (on the diagnostic build of the library)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import ctypes, glob, os, subprocess, sys
+import ctypes
 import numpy as np, torch
 from diffsdfsim_amd import _lib
-src = sorted(glob.glob(os.path.join(_lib.CSRC, "*.hip")))
-diag = os.path.join(_lib.CSRC, "libdiffsdfsim_hip_diag.so")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DDSS_DIAG", "-o", diag] + src)
-L = ctypes.CDLL(diag)
+L = ctypes.CDLL(_lib.build(diag=True))
 names = ["dep fp64 fma", "4 indep fp64 fma chains (per 4)", "2 readlane + fma", "dep LDS read", "dep global read (L2)", "dep fp64 div", "dep fp64 sqrt+add", "dep shuffle+add"]
 n = 20000
 chase = torch.tensor((np.arange(1 << 16) * 37 + 11) & 0xFFFF, dtype=torch.int32, device="cuda")

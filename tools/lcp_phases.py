@@ -1,15 +1,11 @@
-"""Diagnostic: phase shares of lcp_contact_forward_kernel (needs the -DDSS_DIAG build: tools only)."""
+"""Diagnostic: phase shares of lcp_contact_forward_kernel (on the diagnostic build of the library, _lib.build(diag=True))."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import ctypes, glob, os, subprocess, sys
+import ctypes
 import numpy as np, torch
 from diffsdfsim_amd import _lib, scenes
-src = sorted(glob.glob(os.path.join(_lib.CSRC, "*.hip")))
-diag = os.path.join(_lib.CSRC, "libdiffsdfsim_hip_diag.so")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DDSS_DIAG", "-o", diag] + os.environ.get("DSS_DIAG_FLAGS", "").split() + src)
-_lib.LIB_PATH = diag
+_lib.LIB_PATH = _lib.build(diag=True)
 from diffsdfsim_amd.engine import BatchEngine, TorchBackend
-L0 = ctypes.CDLL(diag)
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 KIND = sys.argv[2] if len(sys.argv) > 2 else "stack"      # "sphere": configs[1]'s scenes, stepped until most spheres rest on the floor
 if KIND == "sphere":

@@ -1,9 +1,11 @@
-"""Diagnostic: per-phase time of narrowphase_kernel workgroups (wall_clock64 stamps, 100 MHz)."""
+"""Diagnostic: per-phase time of the lean narrowphase_kernel's work items (wall_clock64 stamps, 100 MHz; on the diagnostic
+build of the library, _lib.build(diag=True))."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes
 import numpy as np, torch
-from diffsdfsim_amd import scenes
+from diffsdfsim_amd import _lib, scenes
+_lib.LIB_PATH = _lib.build(diag=True)
 from diffsdfsim_amd.engine import BatchEngine, TorchBackend
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 KIND = sys.argv[2] if len(sys.argv) > 2 else "stack"      # "sphere": configs[1]'s scenes after 150 steps (most spheres on the floor)
@@ -15,7 +17,7 @@ else:
     E = BatchEngine(spec, maxc=128, max_cand=1024, max_pc=48, strict_no_pen=False, backend=TorchBackend("cuda"))
 np_ = E.nb * (E.nb - 1)
 dbg = torch.zeros(B * np_ * 8, dtype=torch.int64, device="cuda")
-E.W.dbg_stamps = dbg.data_ptr()
+E.be.lib.dss_diag_set_np_stamps(ctypes.c_void_p(dbg.data_ptr()), E.be.stream())
 E.step()
 torch.cuda.synchronize()
 d = dbg.cpu().numpy().reshape(B, np_, 8)

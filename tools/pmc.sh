@@ -4,7 +4,7 @@
 # the same command.  Usage: tools/pmc.sh <config> <steps> [batch]
 #   -> gpurun_out/r3_pmc_config<N>.json (stamped with the library's hash: bench.py reports its numbers only for that build)
 #      gpurun_out/r3_kernel_stats_config<N>.csv        (copy both into profiles/ to have them judged)
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp
 CFG=${1:-3}
 STEPS=${2:-5}
 BATCH=${3:+--batch $3}

@@ -2,7 +2,7 @@
 # Dev aid (GPU box): counters of the dense-LCP kernels under tools/bench_lcp_dense.py --quick (B = 65536; (3,4,0) and (6,8,3)):
 # instruction mix, VALU busy / wave cycles, FETCH_SIZE / WRITE_SIZE in separate passes (MI355X guide, HBM section).
 #   -> gpurun_out/r3_lcp_dense_counters.json   (copy into profiles/ to have it judged)
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp
 OUT=gpurun_out/pmc_dense; rm -rf $OUT; mkdir -p $OUT
 pass() { local name=$1; shift
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -- python3 tools/bench_lcp_dense.py --quick > $OUT/$name.log 2>&1 || echo "pass $name failed"; }

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Dev aid (GPU box): mean duration of igr_advance_kernel and of the network launch by query round (config 4)
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp
 rm -rf gpurun_out/kt && timeout -k 10 500 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/kt -- python3 bench.py --config 4 --steps 40 --warmup 1 --no-cpu > gpurun_out/kt.log 2>&1
 python3 - <<'PY'
 import csv, glob, collections

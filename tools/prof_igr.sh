@@ -1,6 +1,6 @@
 #!/bin/bash
 # Dev aid (GPU box): rocprofv3 evidence for the IGR MLP kernel: kernel stats + fp64-MFMA counters (separate pass).
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+cd "$(dirname "$0")/.." && export TMPDIR=/tmp
 rm -rf gpurun_out/igr_stats gpurun_out/igr_pmc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/igr_stats -- python tools/bench_igr.py > gpurun_out/igr_stats.log 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_WAVE_CYCLES --output-format csv -d gpurun_out/igr_pmc -- python tools/bench_igr.py > gpurun_out/igr_pmc.log 2>&1
