@@ -11,13 +11,13 @@ import subprocess
 
 import torch
 
+from .world_abi import ABI_VERSION, bind
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libdiffsdfsim_hip.so")
 DIAG_LIB_PATH = os.path.join(CSRC, "libdiffsdfsim_hip_diag.so")
 _LIB = None
-
-ABI_VERSION = 2
 
 
 class HipLibraryError(RuntimeError):
@@ -102,11 +102,9 @@ def lib():
                 "%s not found: run `python __graft_entry__.py build` (hipcc, gfx950). "
                 "There is no CPU fallback for the product path." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
-        L.dss_abi_version.restype = ctypes.c_int
-        if L.dss_abi_version() != ABI_VERSION:
+        if L.dss_abi_version() != ABI_VERSION:      # (before bind: a library of another version may lack functions)
             raise HipLibraryError("ABI mismatch: library %d, python %d" % (L.dss_abi_version(), ABI_VERSION))
-        L.dss_lcp_dense_workspace_bytes.restype = ctypes.c_size_t
-        _LIB = L
+        _LIB = bind(L)
     return _LIB
 
 

@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "../../include/diffsdfsim_hip.h"
+#include "launchers.h"
 #include "mfma_f64.h"
 #include "wave_utils.h"
 

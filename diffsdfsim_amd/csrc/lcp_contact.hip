@@ -33,6 +33,7 @@
 
 #include "../../include/diffsdfsim_hip.h"
 #include "kkt_reg.h"
+#include "launchers.h"
 #include "wave_utils.h"
 
 #define DSS_STAMPS lcp   // phase times of the forward kernel in the diagnostic build (tools/lcp_phases.py)
@@ -1107,14 +1108,6 @@ lcp_contact_backward_kernel(const double *Mblk_, const double *A_, const double 
     }
 }
 
-}  // namespace
-namespace dss {
-int lcp_contact_backward_rows(const double *Mblk, const double *A, const double *cop, const int *cbody, const int *nc,
-                              const int *active, int B, int nb, int neq, int maxc, int fric_dirs, const double *x,
-                              const double *lam, const double *slack, const double *nu, const double *dl_dx, double *dMblk,
-                              double *dpvec, double *dcop, double *dA, double *db, int rows, const int *slot, void *stream);
-}
-namespace {
 inline bool dims_ok(int B, int nb, int neq, int maxc, int fd)
 {
     return B > 0 && nb > 0 && neq >= 0 && maxc > 0 && (fd == 4 || fd == 8);

@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "../../include/diffsdfsim_hip.h"
+#include "launchers.h"
 #include "wave_utils.h"
 
 namespace {
@@ -586,16 +587,6 @@ int launch_lcp_dense_wave_backward(const double *Q, const double *G, const doubl
                        ws_bytes_per_system(nz, nineq, neq), in_lds);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }
-
-// lcp_dense_group.hip: eight lanes per system, for nz, nineq, neq <= 8
-bool lcp_dense_group_fits(int nz, int nineq, int neq);
-int launch_lcp_dense_group_forward(const double *Q, const double *p, const double *G, const double *h, const double *A, const double *b,
-                                   const double *F, int B, int nz, int nineq, int neq, double eps, int not_improved_lim, int max_iter,
-                                   int check_spd, double *zhat, double *lam, double *slack, double *nu, int *iters, int *status,
-                                   hipStream_t stream);
-int launch_lcp_dense_group_backward(const double *Q, const double *G, const double *A, const double *F, int B, int nz, int nineq, int neq,
-                                    const double *zhat, const double *lam, const double *slack, const double *nu, const double *dl_dz,
-                                    double *dQ, double *dp, double *dG, double *dh, double *dA, double *db, double *dF, hipStream_t stream);
 }  // namespace dss
 
 extern "C" {

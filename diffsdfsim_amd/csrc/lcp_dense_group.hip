@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "../../include/diffsdfsim_hip.h"
+#include "launchers.h"
 #include "wave_utils.h"
 
 namespace {

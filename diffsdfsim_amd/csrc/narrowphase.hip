@@ -30,7 +30,7 @@
 #define DSS_STAMPS np    // phase times of the lean kernel's work items in the diagnostic build (tools/np_phases.py)
 #endif
 
-
+#include "launchers.h"
 #include "np_common.h"
 
 namespace {
@@ -734,13 +734,10 @@ static inline int np_grid(int B, int nb)
 }
 // enqueue detection at the current pose; results land in (nc_out, body_out, ...)
 #if DSS_ALL_SHAPES
-int launch_igr_rounds(const DssWorld &W, hipStream_t stream);   // narrowphase_igr.hip
 int launch_find_contacts_all(const DssWorld &W, int *nc_out, int *body_out, int *face_out, double *abc_out,
                              double *geom_out, hipStream_t stream)
 {
 #else
-int launch_find_contacts_all(const DssWorld &W, int *nc_out, int *body_out, int *face_out, double *abc_out,
-                             double *geom_out, hipStream_t stream);
 int launch_find_contacts(const DssWorld &W, int *nc_out, int *body_out, int *face_out, double *abc_out,
                          double *geom_out, hipStream_t stream)
 {

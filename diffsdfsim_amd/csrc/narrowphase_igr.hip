@@ -24,13 +24,8 @@
 // falls through to the next stage.  Query slots are reserved with one atomic per item and list; results depend on the
 // point alone, so the order in which items reserve is immaterial and the contact sets are deterministic.
 #define DSS_ALL_SHAPES 1
+#include "launchers.h"
 #include "np_common.h"
-
-namespace dss {
-int launch_igr_pair(const DssIgrNet &N, const double *pts_v, const int *lat_v, const int *n_v, double *sdf_v, const double *pts_g,
-                    const int *lat_g, const int *n_g, double *sdf_g, double *grad_g, const double *latents, int lat_stride, int n_cap,
-                    hipStream_t stream, int est_v, int est_g);
-}
 
 namespace {
 using G = BlockGroup;

@@ -13,12 +13,8 @@
 
 #include "../../include/diffsdfsim_hip.h"
 #include "contact_geom.h"
+#include "launchers.h"
 #include "wave_utils.h"
-
-namespace dss {
-int launch_find_contacts(const DssWorld &W, int *nc_out, int *body_out, int *face_out, double *abc_out,
-                         double *geom_out, hipStream_t stream);
-}
 
 namespace {
 using namespace dss;

@@ -27,6 +27,7 @@
 #if !DSS_ALL_SHAPES
 #include "contact_rev.h"
 #endif
+#include "launchers.h"
 #include "wave_utils.h"
 
 namespace {
@@ -765,8 +766,6 @@ __global__ void __launch_bounds__(64) bwd_post_kernel(DssWorld W_arg, DssAdjoint
 
 #if DSS_ALL_SHAPES
 namespace dss {
-int launch_igr_list(const DssIgrNet &N, const double *pts, const int *lat_idx, const double *latents, int lat_stride,
-                    const int *n_dev, int n_cap, int mode, double *sdf, double *grad, hipStream_t stream, int est);
 void launch_bwd_pre_all(const DssWorld &W, const DssAdjoint &A, hipStream_t stream)
 {
     if (W.igr.W0 && A.igr_bw_idx) {
@@ -781,14 +780,6 @@ void launch_bwd_pre_all(const DssWorld &W, const DssAdjoint &A, hipStream_t stre
 }
 }  // namespace dss
 #else
-namespace dss {
-void launch_bwd_pre_all(const DssWorld &W, const DssAdjoint &A, hipStream_t stream);
-int lcp_contact_backward_rows(const double *Mblk, const double *A, const double *cop, const int *cbody, const int *nc,
-                              const int *active, int B, int nb, int neq, int maxc, int fric_dirs, const double *x,
-                              const double *lam, const double *slack, const double *nu, const double *dl_dx, double *dMblk,
-                              double *dpvec, double *dcop, double *dA, double *db, int rows, const int *slot, void *stream);     // lcp_contact.hip
-}
-
 extern "C" {
 
 size_t dss_adjoint_sizeof(void) { return sizeof(DssAdjoint); }

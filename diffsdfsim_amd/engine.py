@@ -130,7 +130,7 @@ class BatchEngine:
         mt = mesh_table(spec["meshes"], vg)
         L = self.be.lib
         shapes = abi.array_shapes(B, nb, neq, maxc, fric_dirs, max_cand, max_pc, max_sub, len(spec["meshes"]), len(mt["verts"]),
-                                  len(mt["faces"]), L.dss_np_slots(int(B), int(nb)), len(mt["fch_box"]), len(mt["vch_box"]))
+                                  len(mt["faces"]), L.dss_np_slots(B, nb), len(mt["fch_box"]), len(mt["vch_box"]))
         # neural SDF bodies (shape_type 6): network weights + the scratch of the round-based narrow phase
         st_all = np.asarray(spec["shape_type"]).reshape(B, nb)
         igr_b = st_all == abi.SHAPE_IGR
@@ -148,7 +148,7 @@ class BatchEngine:
         for name, shp in shapes.items():
             self.arr[name] = self.be.zeros(shp, abi.NP_DTYPE[kinds[name]])
         if igr_b.any():
-            for k in ("W0", "b0", "Wp", "bh", "W8", "b8"):
+            for k in abi.IGR_NET_FIELDS:
                 w = spec["igr_net"][k]
                 self.arr["igr_" + k] = w if not isinstance(w, np.ndarray) and hasattr(w, "data_ptr") else self.be.from_numpy(np.asarray(w, np.float64))
         host = dict(mt)
@@ -199,11 +199,9 @@ class BatchEngine:
             self.igr_hint[0] = self.igr_items_cap
             W.igr_hint = self.igr_hint.ctypes.data
         self.W = W
-        L.dss_world_sizeof.restype = ctypes.c_size_t
         if L.dss_world_sizeof() != ctypes.sizeof(abi.DssWorld):
             raise RuntimeError("DssWorld layout mismatch: library %d bytes, python mirror %d bytes"
                                % (L.dss_world_sizeof(), ctypes.sizeof(abi.DssWorld)))
-        L.dss_lcp_contact_workspace_bytes.restype = ctypes.c_size_t
         nbytes = L.dss_lcp_contact_workspace_bytes(B, nb, neq, maxc, fric_dirs)
         self.lcp_ws = self.be.zeros((nbytes,), np.uint8)
         self.lcp_ws_bytes = nbytes
@@ -247,6 +245,23 @@ class BatchEngine:
         return self.be.to_numpy(self.arr[name])
 
     # -- stepping --------------------------------------------------------------------------------
+    def _attempt_until_idle(self, n, max_attempts, what):
+        """The attempt loop of step() and run(), entered with `n` active scenes: dss_step_attempt until the 4-byte counter
+        n_active reads zero.  Returns the number of attempts."""
+        L, W = self.be.lib, self.W
+        k = 0
+        while n > 0:
+            self._check(L.dss_step_attempt(ctypes.byref(W), self.be.ptr(self.lcp_ws), self.lcp_ws_bytes, self.be.stream()), "dss_step_attempt")
+            n = self.be.read_int(self.arr["n_active"])
+            if n & abi.N_ACTIVE_OVERFLOW:
+                self._raise_overflow()
+            self._update_igr_hint(k == 0, n == 0)
+            k += 1
+            if k > max_attempts:
+                raise RuntimeError("%s did not finish within %d attempts" % (what, max_attempts))
+        self.attempts += k
+        return k
+
     def step(self, max_attempts=4096, mask=None):
         """One outer step of length dt for every scene (World.step(fixed_dt=True)); with `mask` ([B] of 0/1) only for the
         scenes it selects -- the others keep their state and time (a batch whose scenes are at different times)."""
@@ -260,19 +275,7 @@ class BatchEngine:
             W.step_mask = None
         self._check(L.dss_step_begin(ctypes.byref(W), self.be.stream()), "dss_step_begin")
         n = self.B if mask is None else int(np.asarray(mask, np.int32).sum())
-        k = 0
-        while n > 0:
-            self._check(L.dss_step_attempt(ctypes.byref(W), ctypes.c_void_p(self.be.ptr(self.lcp_ws)),
-                                           ctypes.c_size_t(self.lcp_ws_bytes), self.be.stream()), "dss_step_attempt")
-            n = self.be.read_int(self.arr["n_active"])
-            if n & abi.N_ACTIVE_OVERFLOW:
-                self._raise_overflow()
-            self._update_igr_hint(k == 0, n == 0)
-            k += 1
-            if k > max_attempts:
-                raise RuntimeError("step did not finish within %d attempts" % max_attempts)
-        self.attempts += k
-        return k
+        return self._attempt_until_idle(n, max_attempts, "step")
 
     def run(self, nsteps, max_attempts=1 << 20):
         """`nsteps` outer steps of length dt for every scene, each scene going through its own `World.step()` calls without
@@ -289,21 +292,9 @@ class BatchEngine:
         W.steps_left = self.be.ptr(self.arr["steps_left"])
         try:
             self._check(L.dss_step_begin(ctypes.byref(W), self.be.stream()), "dss_step_begin")
-            n, k = self.B, 0
-            while n > 0:
-                self._check(L.dss_step_attempt(ctypes.byref(W), ctypes.c_void_p(self.be.ptr(self.lcp_ws)),
-                                               ctypes.c_size_t(self.lcp_ws_bytes), self.be.stream()), "dss_step_attempt")
-                n = self.be.read_int(self.arr["n_active"])
-                if n & abi.N_ACTIVE_OVERFLOW:
-                    self._raise_overflow()
-                self._update_igr_hint(k == 0, n == 0)
-                k += 1
-                if k > max_attempts:
-                    raise RuntimeError("run did not finish within %d attempts" % max_attempts)
+            return self._attempt_until_idle(self.B, max_attempts, "run")
         finally:
             W.steps_left = None
-        self.attempts += k
-        return k
 
     def _raise_overflow(self):
         ov = self.get("overflow")
@@ -325,8 +316,7 @@ class BatchEngine:
         before = self.get("nsub").copy()
         k = 0
         while True:
-            self._check(L.dss_step_attempt(ctypes.byref(W), ctypes.c_void_p(self.be.ptr(self.lcp_ws)),
-                                           ctypes.c_size_t(self.lcp_ws_bytes), self.be.stream()), "dss_step_attempt")
+            self._check(L.dss_step_attempt(ctypes.byref(W), self.be.ptr(self.lcp_ws), self.lcp_ws_bytes, self.be.stream()), "dss_step_attempt")
             k += 1
             if self.get("overflow").any():
                 self._raise_overflow()
@@ -351,9 +341,7 @@ class BatchEngine:
             for n, _k in abi.ADJ_FIELDS:
                 setattr(A, n, self.be.ptr(self.adj[n]) if n in self.adj else None)
             self.A = A
-            L = self.be.lib
-            L.dss_adjoint_sizeof.restype = ctypes.c_size_t
-            if L.dss_adjoint_sizeof() != ctypes.sizeof(abi.DssAdjoint):
+            if self.be.lib.dss_adjoint_sizeof() != ctypes.sizeof(abi.DssAdjoint):
                 raise RuntimeError("DssAdjoint layout mismatch")
         return self.adj
 

@@ -11,8 +11,6 @@ Differences that are by design:
   * the backward re-factors instead of keeping Q_LU / S_LU / R alive on the tape;
   * batch-wide termination tests are applied per system.
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 
@@ -70,11 +68,10 @@ def lcp_dense_forward(Q, p, G, h, A, b, F, eps, not_improved_lim, max_iter, chec
     status = torch.zeros(B, dtype=torch.int32, device=dev)
     nbytes = L.dss_lcp_dense_workspace_bytes(B, nz, nineq, neq)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    rc = L.dss_lcp_dense_forward(_lib.ptr(Q), _lib.ptr(p), _lib.ptr(G), _lib.ptr(h), _lib.ptr(A), _lib.ptr(b),
-                                 _lib.ptr(F), B, nz, nineq, neq, ctypes.c_double(eps), int(not_improved_lim),
-                                 int(max_iter), int(bool(check_spd)), _lib.ptr(zhat), _lib.ptr(lam), _lib.ptr(slack),
-                                 _lib.ptr(nu), _lib.ptr(iters), _lib.ptr(status), _lib.ptr(ws),
-                                 ctypes.c_size_t(nbytes), _lib.stream_ptr(dev))
+    rc = L.dss_lcp_dense_forward(_lib.ptr(Q), _lib.ptr(p), _lib.ptr(G), _lib.ptr(h), _lib.ptr(A), _lib.ptr(b), _lib.ptr(F),
+                                 B, nz, nineq, neq, eps, int(not_improved_lim), int(max_iter), int(bool(check_spd)), _lib.ptr(zhat),
+                                 _lib.ptr(lam), _lib.ptr(slack), _lib.ptr(nu), _lib.ptr(iters), _lib.ptr(status), _lib.ptr(ws), nbytes,
+                                 _lib.stream_ptr(dev))
     _lib.check(rc, "dss_lcp_dense_forward")
     return zhat, lam, slack, nu, iters, status
 
@@ -93,7 +90,7 @@ def lcp_dense_backward(Q, G, A, F, zhat, lam, slack, nu, dl_dz):
     rc = L.dss_lcp_dense_backward(_lib.ptr(Q), _lib.ptr(G), _lib.ptr(A), _lib.ptr(F), B, nz, nineq, neq,
                                   _lib.ptr(zhat), _lib.ptr(lam), _lib.ptr(slack), _lib.ptr(nu), _lib.ptr(dl_dz),
                                   _lib.ptr(dQ), _lib.ptr(dp), _lib.ptr(dG), _lib.ptr(dh), _lib.ptr(dA), _lib.ptr(db),
-                                  _lib.ptr(dF), _lib.ptr(ws), ctypes.c_size_t(nbytes), _lib.stream_ptr(dev))
+                                  _lib.ptr(dF), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
     _lib.check(rc, "dss_lcp_dense_backward")
     return dQ, dp, dG, dh, dA, db, dF
 

@@ -31,9 +31,8 @@ def sdf_query(shape_type, prm, pts, return_grads=True, return_overlapmask=False)
     grad = torch.empty(n, 3, dtype=torch.float64, device=pts.device) if return_grads else None
     mask = torch.empty(n, dtype=torch.uint8, device=pts.device) if return_overlapmask else None
     if n:
-        rc = _lib.lib().dss_sdf_query(int(shape_type), prm_h.ctypes.data_as(_lib.ctypes.c_void_p), _lib.ptr(pts), int(n),
-                                      _lib.ptr(sdf), _lib.ptr(grad) if return_grads else None,
-                                      _lib.ptr(mask) if return_overlapmask else None, _lib.stream_ptr(pts.device))
+        rc = _lib.lib().dss_sdf_query(int(shape_type), prm_h.ctypes.data, _lib.ptr(pts), int(n), _lib.ptr(sdf), _lib.ptr(grad),
+                                      _lib.ptr(mask), _lib.stream_ptr(pts.device))      # (grad, mask: None -> NULL)
         _lib.check(rc, "dss_sdf_query")
     out = (sdf,) + ((grad,) if return_grads else ()) + ((mask.bool(),) if return_overlapmask else ())
     return out if len(out) > 1 else out[0]
@@ -47,10 +46,8 @@ def grid_sdf_query(grid, scale, pts, return_grads=True, return_overlapmask=False
     grad = torch.empty(n, 3, dtype=torch.float64, device=pts.device) if return_grads else None
     mask = torch.empty(n, dtype=torch.uint8, device=pts.device) if return_overlapmask else None
     if n:
-        rc = _lib.lib().dss_grid_sdf_query(_lib.ptr(grid), int(grid.shape[0]), int(grid.shape[1]), int(grid.shape[2]),
-                                           _lib.ctypes.c_double(float(scale)), _lib.ptr(pts), int(n), _lib.ptr(sdf),
-                                           _lib.ptr(grad) if return_grads else None,
-                                           _lib.ptr(mask) if return_overlapmask else None, _lib.stream_ptr(pts.device))
+        rc = _lib.lib().dss_grid_sdf_query(_lib.ptr(grid), int(grid.shape[0]), int(grid.shape[1]), int(grid.shape[2]), float(scale),
+                                           _lib.ptr(pts), int(n), _lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(mask), _lib.stream_ptr(pts.device))
         _lib.check(rc, "dss_grid_sdf_query")
     out = (sdf,) + ((grad,) if return_grads else ()) + ((mask.bool(),) if return_overlapmask else ())
     return out if len(out) > 1 else out[0]
@@ -107,7 +104,7 @@ class _MeshInertiaFn(torch.autograd.Function):
         g = _dev(gJ).reshape(9)
         gv = torch.empty_like(V)
         rc = _lib.lib().dss_mesh_inertia_backward(_lib.ptr(V), _lib.ptr(F), int(V.shape[0]), int(F.shape[0]),
-                                                  _lib.ctypes.c_double(ctx.mass), _lib.ptr(g), _lib.ptr(gv), _lib.stream_ptr(V.device))
+                                                  ctx.mass, _lib.ptr(g), _lib.ptr(gv), _lib.stream_ptr(V.device))
         _lib.check(rc, "dss_mesh_inertia_backward")
         gm = None if ctx.mdev is None else ((g.reshape(3, 3) * J).sum() / ctx.mass).to(ctx.mdev)     # J is linear in the mass
         return gv.to(ctx.vdev), None, gm

@@ -34,18 +34,16 @@ def marching_cubes(phi, iso=0.0):
     phi = _dev(phi)
     n0, n1, n2 = phi.shape
     L = _lib.lib()
-    L.dss_mc_workspace_bytes.restype = _lib.ctypes.c_size_t
     nbytes = L.dss_mc_workspace_bytes(n0, n1, n2)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=phi.device)
     tot = torch.zeros(2, dtype=torch.int32, device=phi.device)
     ntri, tri = _tables(phi.device)
     st = _lib.stream_ptr(phi.device)
-    _lib.check(L.dss_mc_count(_lib.ptr(phi), n0, n1, n2, _lib.ctypes.c_double(iso), _lib.ptr(ntri), _lib.ptr(ws),
-                              _lib.ctypes.c_size_t(nbytes), _lib.ptr(tot), st), "dss_mc_count")
+    _lib.check(L.dss_mc_count(_lib.ptr(phi), n0, n1, n2, iso, _lib.ptr(ntri), _lib.ptr(ws), nbytes, _lib.ptr(tot), st), "dss_mc_count")
     nv, nf = [int(x) for x in tot.cpu()]          # the one host read: sizes of the outputs
     verts = torch.empty(max(nv, 1), 3, dtype=torch.float64, device=phi.device)
     faces = torch.empty(max(nf, 1), 3, dtype=torch.int32, device=phi.device)
-    _lib.check(L.dss_mc_emit(_lib.ptr(phi), n0, n1, n2, _lib.ctypes.c_double(iso), _lib.ptr(ntri), _lib.ptr(tri),
+    _lib.check(L.dss_mc_emit(_lib.ptr(phi), n0, n1, n2, iso, _lib.ptr(ntri), _lib.ptr(tri),
                              mc_tables.MAX_TRI, _lib.ptr(ws), _lib.ptr(verts), _lib.ptr(faces), st), "dss_mc_emit")
     return verts[:nv], faces[:nf]
 
@@ -87,7 +85,7 @@ class _PrimitiveMeshSDF(torch.autograd.Function):
         verts, p = ctx.saved_tensors
         out = torch.empty(4, dtype=torch.float64, device=verts.device)
         prm_h = np.zeros(4); prm_h[: p.numel()] = p.numpy().reshape(-1)
-        rc = _lib.lib().dss_meshsdf_backward(int(ctx.shape_type), prm_h.ctypes.data_as(_lib.ctypes.c_void_p), _lib.ptr(verts),
+        rc = _lib.lib().dss_meshsdf_backward(int(ctx.shape_type), prm_h.ctypes.data, _lib.ptr(verts),
                                              _lib.ptr(grad_v.contiguous()), int(verts.shape[0]), _lib.ptr(out),
                                              _lib.stream_ptr(verts.device))
         _lib.check(rc, "dss_meshsdf_backward")

@@ -7,17 +7,11 @@
 (``dss_contacts2d_forward`` / ``_backward``, include/diffsdfsim_hip.h §R18): circles and convex polygons, gradients to
 positions, radii and vertices.  `contacts2d` is the batched operator (P pairs per launch) for callers that hold many scenes.
 """
-import ctypes
-
 import torch
 
 from .. import _lib
 
 MAXV = 8      # DSS_C2D_MAXV
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
 
 
 def _device_forward(kind, nv, pos, rad, verts, sat_in, eps):
@@ -27,11 +21,10 @@ def _device_forward(kind, nv, pos, rad, verts, sat_in, eps):
     sat_out = torch.empty_like(sat_in)
     count = torch.empty(P, dtype=torch.int32, device=pos.device)
     out = torch.empty(P, 2, 7, dtype=torch.float64, device=pos.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)
-    rc = L.dss_contacts2d_forward(P, maxv, _ptr(kind), _ptr(nv), _ptr(pos), _ptr(rad), _ptr(verts), _ptr(sat_in),
-                                  ctypes.c_double(eps), _ptr(sat_out), _ptr(count), _ptr(out), stream)
-    if rc != 0:
-        raise _lib.HipLibraryError("dss_contacts2d_forward failed (%d)" % rc)
+    ptr = _lib.ptr
+    rc = L.dss_contacts2d_forward(P, maxv, ptr(kind), ptr(nv), ptr(pos), ptr(rad), ptr(verts), ptr(sat_in), eps,
+                                  ptr(sat_out), ptr(count), ptr(out), _lib.stream_ptr(pos.device))
+    _lib.check(rc, "dss_contacts2d_forward")
     return out, count, sat_out
 
 
@@ -39,11 +32,10 @@ def _device_backward(kind, nv, pos, rad, verts, sat_in, eps, gout):
     L = _lib.lib()
     P, maxv = pos.shape[1], verts.shape[2]
     g_pos, g_rad, g_verts = torch.zeros_like(pos), torch.zeros_like(rad), torch.zeros_like(verts)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream)
-    rc = L.dss_contacts2d_backward(P, maxv, _ptr(kind), _ptr(nv), _ptr(pos), _ptr(rad), _ptr(verts), _ptr(sat_in),
-                                   ctypes.c_double(eps), _ptr(gout), _ptr(g_pos), _ptr(g_rad), _ptr(g_verts), stream)
-    if rc != 0:
-        raise _lib.HipLibraryError("dss_contacts2d_backward failed (%d)" % rc)
+    ptr = _lib.ptr
+    rc = L.dss_contacts2d_backward(P, maxv, ptr(kind), ptr(nv), ptr(pos), ptr(rad), ptr(verts), ptr(sat_in), eps,
+                                   ptr(gout), ptr(g_pos), ptr(g_rad), ptr(g_verts), _lib.stream_ptr(pos.device))
+    _lib.check(rc, "dss_contacts2d_backward")
     return g_pos, g_rad, g_verts
 
 

@@ -25,11 +25,9 @@ class HipPdipmEngine(Engine):
         E.arr["vel"].copy_(world.vel.detach())
         E.arr["dt_try"].fill_(float(dt))
         E.arr["active"].fill_(1)
-        rc = E.be.lib.dss_solve_dynamics(ctypes.byref(E.W), ctypes.c_void_p(E.be.ptr(E.lcp_ws)),
-                                         ctypes.c_size_t(E.lcp_ws_bytes), E.be.stream())
+        rc = E.be.lib.dss_solve_dynamics(ctypes.byref(E.W), E.be.ptr(E.lcp_ws), E.lcp_ws_bytes, E.be.stream())
         E.arr["active"].fill_(0)
-        if rc != 0:
-            raise RuntimeError("dss_solve_dynamics failed with code %d" % rc)
+        E._check(rc, "dss_solve_dynamics")
         return (-E.arr["x"][0]).clone()
 
 

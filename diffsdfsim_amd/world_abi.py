@@ -1,18 +1,67 @@
-"""ctypes mirror of ``DssWorld`` (include/diffsdfsim_hip.h, section B3) and array allocation.
+"""The C ABI of include/diffsdfsim_hip.h as ctypes sees it: constants, function prototypes, struct mirrors, array shapes.
 
-The field order below IS the struct layout; ``dss_world_sizeof()`` is checked against it when the
-world is first bound to the library, so a mismatch fails loudly instead of corrupting memory, and
-tests/test_abi.py checks the names and their order against the header's declarations.
+The header is the documentation and the check, the tables below are the binding: ``bind()`` gives every function of a
+loaded library its ``argtypes`` / ``restype``, so callers pass plain Python ints, floats and pointers.  The field order of
+``FIELDS`` IS the struct layout; ``dss_world_sizeof()`` is checked against it when the world is first bound to the library.
+tests/test_abi.py checks constants, prototypes and field names and their order against the header's text.
 """
 import ctypes
 
 import numpy as np
 
+# the header's #defines (DSS_<name>)
+ABI_VERSION = 2
 CAND_FIELDS = 28
+CSCR_ROWS = 56
 N_ACTIVE_OVERFLOW = 1 << 30
 SHAPE_BOX, SHAPE_SPHERE, SHAPE_CYLINDER, SHAPE_BOX_ROUNDED, SHAPE_BRICK, SHAPE_BOWL, SHAPE_IGR, SHAPE_GRID = 0, 1, 2, 3, 4, 5, 6, 7
+IGR_HDR, IGR_ROUNDS = 16, 42
 
 _I, _D, _P = ctypes.c_int, ctypes.c_double, ctypes.c_void_p
+
+# name: (return kind, argument kinds): 'p' any pointer (tensor, struct by reference, stream; None = NULL), 'i' int, 'd' double,
+# 'z' size_t, 'v' void.  In the header's order, one section per line or two.
+PROTOTYPES = {
+    "dss_abi_version": ("i", ""),
+    "dss_lcp_dense_workspace_bytes": ("z", "iiii"), "dss_lcp_dense_forward": ("i", "pppppppiiiidiiipppppppzp"),
+    "dss_lcp_dense_backward": ("i", "ppppiiiipppppppppppppzp"),
+    "dss_lcp_contact_workspace_bytes": ("z", "iiiii"), "dss_lcp_contact_forward": ("i", "ppppppppiiiiidiipppppppzp"),
+    "dss_lcp_contact_backward": ("i", "ppppppiiiiippppppppppp"),
+    "dss_world_sizeof": ("z", ""), "dss_np_slots": ("i", "ii"), "dss_step_begin": ("i", "pp"), "dss_step_attempt": ("i", "ppzp"),
+    "dss_solve_dynamics": ("i", "ppzp"), "dss_find_contacts": ("i", "pp"),
+    "dss_adjoint_sizeof": ("z", ""), "dss_step_backward": ("i", "ppp"),
+    "dss_igr_packed_doubles": ("z", ""), "dss_igr_query_list": ("i", "ppppipiippp"), "dss_igr_query": ("i", "ppppppppippp"),
+    "dss_igr_query_latent_grad": ("i", "ppppppppippp"),
+    "dss_sdf_query": ("i", "ippipppp"), "dss_mesh_inertia": ("i", "pppppipppp"), "dss_grid_sdf_query": ("i", "piiidpipppp"),
+    "dss_mesh_inertia_backward": ("i", "ppiidppp"), "dss_selftest_div3": ("i", "ppipp"), "dss_selftest_sqrt": ("i", "pipp"),
+    "dss_mc_workspace_bytes": ("z", "iii"), "dss_mc_count": ("i", "piiidppzpp"), "dss_mc_emit": ("i", "piiidppipppp"),
+    "dss_meshsdf_backward": ("i", "ipppipp"),
+    "dss_contacts2d_forward": ("i", "iippppppdpppp"), "dss_contacts2d_backward": ("i", "iippppppdppppp"),
+}
+# outside the public header, bound where a library exports them: the diagnostic build (csrc/diag_stamps.h,
+# csrc/diag_latency.hip) and the CPU emulator's test hook (tests/emu/lcp_dense_wave.cpp)
+OPTIONAL_PROTOTYPES = {
+    "dss_diag_set_lcp_stamps": ("v", "pp"), "dss_diag_set_np_stamps": ("v", "pp"), "dss_diag_latency": ("v", "iiippppp"),
+    "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"],
+}
+_CTYPE = {"p": _P, "i": _I, "d": _D, "z": ctypes.c_size_t, "v": None}
+
+
+def bind(L):
+    """Set argtypes / restype of every function of the tables on the loaded library L; returns L.  A function of the
+    header that L does not export raises AttributeError, an optional one is skipped."""
+    for name, (ret, args) in {**PROTOTYPES, **{n: p for n, p in OPTIONAL_PROTOTYPES.items() if hasattr(L, n)}}.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = _CTYPE[ret], [_CTYPE[k] for k in args]
+    return L
+
+
+IGR_NET_FIELDS = ("W0", "b0", "Wp", "bh", "W8", "b8")
+
+
+class DssIgrNet(ctypes.Structure):
+    _fields_ = [(k, _P) for k in IGR_NET_FIELDS]
+
 
 # (name, kind) kind: 'i' int scalar, 'd' double scalar, 'pd' double*, 'pi' int*, 'pb' uint8*
 FIELDS = [
@@ -43,13 +92,12 @@ FIELDS = [
     ("tp_nc", "pi"), ("tp_body", "pi"), ("tp_face", "pi"), ("tp_flags", "pi"), ("tp_t", "pd"),
     ("ev_lcp_start", "ev"), ("ev_lcp_stop", "ev"), ("ev_np_start", "ev"), ("ev_np_stop", "ev"),
     # neural SDF bodies: DssIgrNet (six pointers), capacities, the round-based narrow phase's item state and query lists
-    ("igr_W0", "pd"), ("igr_b0", "pd"), ("igr_Wp", "pd"), ("igr_bh", "pd"), ("igr_W8", "pd"), ("igr_b8", "pd"),
+    *[("igr_" + k, "pd") for k in IGR_NET_FIELDS],
     ("igr_items_cap", "i"), ("igr_qcap", "i"), ("igr_rounds", "i"),
     ("igr_list", "pi"), ("igr_hdr", "pi"), ("igr_cface", "pi"), ("igr_cstate", "pi"), ("igr_cbuf", "pd"),
     ("igr_qpts", "pd"), ("igr_qlat", "pi"), ("igr_qtag", "pi"), ("igr_qsdf", "pd"), ("igr_qgrad", "pd"), ("igr_qn", "pi"),
     ("igr_hint", "ev"), ("igr_ev", "ev"),
 ]
-IGR_HDR, IGR_ROUNDS = 16, 42
 
 
 class DssWorld(ctypes.Structure):
@@ -128,5 +176,5 @@ def adjoint_shapes(B, nb, maxc, fd, NV=1, igr=False):
         "g_mass": (B, nb), "g_inertia": (B, nb, 9), "g_rest": (B, nb), "g_fric": (B, nb), "g_fext": (B, nb, 6),
         "g_prm": (B, nb, 3), "g_verts": (NV, 3), "cur_slot": (B,), "lo_slot": (B,), "bw_active": (B,),
         "a_x": (B, 6 * nb), "dMblk": (B, nb, 36), "dpvec": (B, 6 * nb), "dcop": (B, NFc, maxc),
-        "cscr": (B, 56, maxc), "bw_nc": (B,),
+        "cscr": (B, CSCR_ROWS, maxc), "bw_nc": (B,),
     }

@@ -2,8 +2,14 @@
 import ctypes
 import os
 import subprocess
+import sys
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(_HERE, "..", ".."))
+from diffsdfsim_amd import mc_tables, world_abi  # noqa: E402
+
 _LIB = None
 
 
@@ -11,16 +17,12 @@ def lib():
     global _LIB
     subprocess.check_call(["make", "-s", "-C", _HERE])
     if _LIB is None:
-        _LIB = ctypes.CDLL(os.path.join(_HERE, "_build", "libdss_emu.so"))
-        _LIB.dss_lcp_dense_workspace_bytes.restype = ctypes.c_size_t
+        _LIB = world_abi.bind(ctypes.CDLL(os.path.join(_HERE, "_build", "libdss_emu.so")))
     return _LIB
 
 
-import numpy as np  # noqa: E402
-
-
-def _p(a):
-    return ctypes.c_void_p(a.ctypes.data) if a is not None and a.size else ctypes.c_void_p(0)
+def _p(a):      # address of a host array (None / empty -> NULL)
+    return a.ctypes.data if a is not None and a.size else None
 
 
 def _c(a, dtype=np.float64):
@@ -39,8 +41,7 @@ def lcp_dense_forward(Q, p, G, h, A, b, F, eps=1e-12, nil=3, max_iter=20, check_
     ws = np.zeros(nbytes, np.uint8)
     fn = L.dss_emu_lcp_dense_wave_forward if wave else L.dss_lcp_dense_forward
     rc = fn(_p(Q), _p(p), _p(G), _p(h), _p(A), _p(b), _p(F), B, nz, nineq, neq,
-            ctypes.c_double(eps), nil, max_iter, int(check_spd), _p(zhat), _p(lam), _p(slack),
-            _p(nu), _p(iters), _p(status), _p(ws), ctypes.c_size_t(nbytes), None)
+            eps, nil, max_iter, int(check_spd), _p(zhat), _p(lam), _p(slack), _p(nu), _p(iters), _p(status), _p(ws), nbytes, None)
     assert rc == 0, rc
     return zhat, lam, slack, nu, iters, status
 
@@ -55,15 +56,13 @@ def lcp_dense_backward(Q, G, A, F, zhat, lam, slack, nu, dl):
     nbytes = L.dss_lcp_dense_workspace_bytes(B, nz, nineq, neq)
     ws = np.zeros(nbytes, np.uint8)
     rc = L.dss_lcp_dense_backward(_p(Q), _p(G), _p(A), _p(F), B, nz, nineq, neq, _p(zhat), _p(lam), _p(slack), _p(nu),
-                                  _p(dl), _p(dQ), _p(dp), _p(dG), _p(dh), _p(dA), _p(db), _p(dF), _p(ws),
-                                  ctypes.c_size_t(nbytes), None)
+                                  _p(dl), _p(dQ), _p(dp), _p(dG), _p(dh), _p(dA), _p(db), _p(dF), _p(ws), nbytes, None)
     assert rc == 0, rc
     return dQ, dp, dG, dh, dA, db, dF
 
 
 def lcp_contact_forward(P, eps=1e-12, nil=3, max_iter=10):
     L = lib()
-    L.dss_lcp_contact_workspace_bytes.restype = ctypes.c_size_t
     B, nb, neq, maxc, fd = P["Mblk"].shape[0], P["nb"], P["neq"], P["maxc"], P["fd"]
     NR = fd + 2; nz = 6 * nb
     Mblk, pvec, A, bvec, cop = (_c(P[k]) for k in ("Mblk", "pvec", "A", "bvec", "cop"))
@@ -73,8 +72,7 @@ def lcp_contact_forward(P, eps=1e-12, nil=3, max_iter=10):
     nbytes = L.dss_lcp_contact_workspace_bytes(B, nb, neq, maxc, fd)
     ws = np.zeros(nbytes, np.uint8)
     rc = L.dss_lcp_contact_forward(_p(Mblk), _p(pvec), _p(A), _p(bvec), _p(cop), _p(cbody), _p(nc), None, B, nb, neq, maxc, fd,
-                                   ctypes.c_double(eps), nil, max_iter, _p(x), _p(lam), _p(slack), _p(nu), _p(iters),
-                                   _p(status), _p(ws), ctypes.c_size_t(nbytes), None)
+                                   eps, nil, max_iter, _p(x), _p(lam), _p(slack), _p(nu), _p(iters), _p(status), _p(ws), nbytes, None)
     assert rc == 0, rc
     return x, lam, slack, nu, iters, status
 
@@ -151,7 +149,7 @@ def grid_sdf_query(grid, scale, pts):
     L = lib()
     G = _c(grid); pts = _c(pts); n = len(pts)
     sdf = np.zeros(n); grad = np.zeros((n, 3)); mask = np.zeros(n, np.uint8)
-    rc = L.dss_grid_sdf_query(_p(G), G.shape[0], G.shape[1], G.shape[2], ctypes.c_double(scale), _p(pts), n, _p(sdf), _p(grad),
+    rc = L.dss_grid_sdf_query(_p(G), G.shape[0], G.shape[1], G.shape[2], scale, _p(pts), n, _p(sdf), _p(grad),
                               _p(mask), None)
     assert rc == 0
     return sdf, grad, mask.astype(bool)
@@ -168,20 +166,16 @@ def mesh_inertia(verts, faces, mass):
 
 
 def marching_cubes(phi, iso=0.0):
-    import sys as _sys
-    _sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-    from diffsdfsim_amd import mc_tables
     L = lib()
     ntri, tri, _ = mc_tables.tables()
     phi = _c(phi); n0, n1, n2 = phi.shape
-    L.dss_mc_workspace_bytes.restype = ctypes.c_size_t
     nb = L.dss_mc_workspace_bytes(n0, n1, n2)
     ws = np.zeros(nb, np.uint8); tot = np.zeros(2, np.int32)
     ntri_c = _c(ntri, np.int32); tri_c = _c(tri, np.int8)
-    rc = L.dss_mc_count(_p(phi), n0, n1, n2, ctypes.c_double(iso), _p(ntri_c), _p(ws), ctypes.c_size_t(nb), _p(tot), None)
+    rc = L.dss_mc_count(_p(phi), n0, n1, n2, iso, _p(ntri_c), _p(ws), nb, _p(tot), None)
     assert rc == 0
     V = np.zeros((max(int(tot[0]), 1), 3)); F = np.zeros((max(int(tot[1]), 1), 3), np.int32)
-    rc = L.dss_mc_emit(_p(phi), n0, n1, n2, ctypes.c_double(iso), _p(ntri_c), _p(tri_c), mc_tables.MAX_TRI, _p(ws), _p(V), _p(F), None)
+    rc = L.dss_mc_emit(_p(phi), n0, n1, n2, iso, _p(ntri_c), _p(tri_c), mc_tables.MAX_TRI, _p(ws), _p(V), _p(F), None)
     assert rc == 0
     return V[: tot[0]], F[: tot[1]]
 
@@ -199,7 +193,7 @@ def meshsdf_backward(shape_type, unit_prm, unit_verts, gbar):
 def mesh_inertia_backward(verts, faces, mass, gJ):
     L = lib()
     V = _c(verts); F = _c(faces, np.int32); g = _c(gJ).reshape(9); out = np.zeros_like(V)
-    rc = L.dss_mesh_inertia_backward(_p(V), _p(F), len(V), len(F), ctypes.c_double(mass), _p(g), _p(out), None)
+    rc = L.dss_mesh_inertia_backward(_p(V), _p(F), len(V), len(F), mass, _p(g), _p(out), None)
     assert rc == 0
     return out
 
@@ -211,7 +205,7 @@ def contacts2d_forward(kind, nv, pos, rad, verts, sat_in, eps):
     pos, rad, verts = (_c(x) for x in (pos, rad, verts))
     P, maxv = pos.shape[1], verts.shape[2]
     sat_out = np.zeros((2, P), np.int32); count = np.zeros(P, np.int32); out = np.zeros((P, 2, 7))
-    rc = L.dss_contacts2d_forward(P, maxv, _p(kind), _p(nv), _p(pos), _p(rad), _p(verts), _p(sat_in), ctypes.c_double(eps),
+    rc = L.dss_contacts2d_forward(P, maxv, _p(kind), _p(nv), _p(pos), _p(rad), _p(verts), _p(sat_in), eps,
                                   _p(sat_out), _p(count), _p(out), None)
     assert rc == 0, rc
     return out, count, sat_out
@@ -223,7 +217,7 @@ def contacts2d_backward(kind, nv, pos, rad, verts, sat_in, eps, gout):
     pos, rad, verts, gout = (_c(x) for x in (pos, rad, verts, gout))
     P, maxv = pos.shape[1], verts.shape[2]
     g_pos, g_rad, g_verts = np.zeros_like(pos), np.zeros_like(rad), np.zeros_like(verts)
-    rc = L.dss_contacts2d_backward(P, maxv, _p(kind), _p(nv), _p(pos), _p(rad), _p(verts), _p(sat_in), ctypes.c_double(eps),
+    rc = L.dss_contacts2d_backward(P, maxv, _p(kind), _p(nv), _p(pos), _p(rad), _p(verts), _p(sat_in), eps,
                                    _p(gout), _p(g_pos), _p(g_rad), _p(g_verts), None)
     assert rc == 0, rc
     return g_pos, g_rad, g_verts

@@ -1,5 +1,5 @@
 """CPU: the C-ABI library builds, loads and exports every symbol include/*.h declares; the ctypes mirrors of the structs
-list the header's fields in the header's order."""
+list the header's fields in the header's order; the prototype table and the constants of world_abi follow the header."""
 import ctypes
 import glob
 import os
@@ -32,6 +32,27 @@ def struct_fields(name):
     return names
 
 
+def header_prototypes():
+    """{name: (return kind, argument kinds)} of every dss_* prototype of the header, in world_abi.PROTOTYPES' spelling:
+    an argument with `*` is a pointer 'p', otherwise its type is int 'i', double 'd' or size_t 'z'."""
+    text = re.sub(r"typedef struct (\w+) \{.*?\} \1;", "", header_text(), flags=re.S)
+    kind = {"int": "i", "double": "d", "size_t": "z", "void": "v"}
+    protos = {}
+    for ret, name, args in re.findall(r"\b(int|size_t|void)\s+(dss_\w+)\s*\(([^)]*)\)\s*;", text):
+        assert name not in protos, "%s declared twice" % name
+        args = [] if args.strip() in ("", "void") else [a.strip() for a in args.split(",")]
+        protos[name] = (kind[ret], "".join("p" if "*" in a else kind[a.replace("const ", "").split()[0]] for a in args))
+    return protos
+
+
+def header_defines():
+    """{name: value} of the header's #defines whose value is an integer expression."""
+    out = {}
+    for name, val in re.findall(r"^#define (DSS_\w+)[ \t]+(\(?-?\d[\d <()-]*?)[ \t]*$", header_text(), flags=re.M):
+        out[name] = eval(val, {"__builtins__": {}})
+    return out
+
+
 def test_library_exports_every_declared_symbol():
     from diffsdfsim_amd import _lib
     _lib.build()
@@ -43,6 +64,37 @@ def test_library_exports_every_declared_symbol():
     assert L.dss_abi_version() == _lib.ABI_VERSION
     for s in ("dss_diag_set_lcp_stamps", "dss_diag_set_np_stamps", "dss_diag_latency"):
         assert not hasattr(L, s), "diagnostic export %s in the product library" % s
+    # _lib.lib() has bound every declared function: none is left to ctypes' guess (a bare int passed as a 32-bit C int)
+    from diffsdfsim_amd import world_abi
+    ctype = {"i": ctypes.c_int, "z": ctypes.c_size_t}
+    for s in syms:
+        ret, args = world_abi.PROTOTYPES[s]
+        fn = getattr(L, s)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(args), "%s not bound" % s
+        assert fn.restype is ctype[ret], s
+
+
+def test_prototype_table_follows_the_header():
+    from diffsdfsim_amd import world_abi
+    protos = header_prototypes()
+    assert sorted(protos) == declared_symbols() and len(protos) == 31
+    assert sorted(world_abi.PROTOTYPES) == sorted(protos)
+    for name, sig in protos.items():
+        assert world_abi.PROTOTYPES[name] == sig, name
+    assert not set(world_abi.OPTIONAL_PROTOTYPES) & set(protos)
+
+
+def test_constants_follow_the_header():
+    from diffsdfsim_amd import _lib, world_abi
+    d = header_defines()
+    assert _lib.ABI_VERSION == world_abi.ABI_VERSION == d["DSS_ABI_VERSION"]
+    for name in ("CAND_FIELDS", "N_ACTIVE_OVERFLOW", "IGR_HDR", "IGR_ROUNDS", "CSCR_ROWS"):
+        assert getattr(world_abi, name) == d["DSS_" + name], name
+    shapes = sorted(n for n in d if n.startswith("DSS_SHAPE_"))
+    assert len(shapes) == 8 and sorted(d[n] for n in shapes) == list(range(8))
+    for name in shapes:
+        assert getattr(world_abi, name[4:]) == d[name], name
+    assert sorted(n for n in vars(world_abi) if n.startswith("SHAPE_")) == [n[4:] for n in shapes]
 
 
 def test_struct_mirrors_follow_the_header():
@@ -50,6 +102,7 @@ def test_struct_mirrors_follow_the_header():
     from diffsdfsim_amd import world_abi
     assert struct_fields("DssWorld") == [n for n, _ in world_abi.FIELDS]
     assert struct_fields("DssAdjoint") == [n for n, _ in world_abi.ADJ_FIELDS]
+    assert struct_fields("DssIgrNet") == [n for n, _ in world_abi.DssIgrNet._fields_] == list(world_abi.IGR_NET_FIELDS)
 
 
 def test_product_path_refuses_cpu_tensors():

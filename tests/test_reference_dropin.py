@@ -272,8 +272,7 @@ def test_reference_3d_world_on_the_builds_engine_plugin():
                 A["c_geom"][0, 0:3, c] = nr.detach().numpy(); A["c_geom"][0, 3:6, c] = p1.detach().numpy()
                 A["c_geom"][0, 6:9, c] = p2.detach().numpy(); A["c_geom"][0, 9, c] = float(pen)
             A["dt_try"][0] = float(dt); A["active"][0] = 1
-            rc = E.be.lib.dss_solve_dynamics(ctypes.byref(E.W), ctypes.c_void_p(E.be.ptr(E.lcp_ws)),
-                                             ctypes.c_size_t(E.lcp_ws_bytes), E.be.stream())
+            rc = E.be.lib.dss_solve_dynamics(ctypes.byref(E.W), E.be.ptr(E.lcp_ws), E.lcp_ws_bytes, E.be.stream())
             A["active"][0] = 0
             assert rc == 0
             return torch.tensor(-A["x"][0].copy())

@@ -4,19 +4,17 @@ import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsdfsim_amd import _lib, scenes
 from diffsdfsim_amd.igr import pack_weights
+from diffsdfsim_amd.world_abi import IGR_NET_FIELDS, DssIgrNet
 P = pack_weights(*scenes.geometric_init_weights(0, 0.5))
 L = _lib.lib()
-class Net(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_void_p) for k in ("W0", "b0", "Wp", "bh", "W8", "b8")]
-net = Net(*[P[k].data_ptr() for k in ("W0", "b0", "Wp", "bh", "W8", "b8")])
+net = DssIgrNet(*[P[k].data_ptr() for k in IGR_NET_FIELDS])
 for n in (240_000, 60_000, 1_000_000):
     pts = torch.rand(n, 3, dtype=torch.float64, device="cuda") * 1.6 - 0.8
     lat = torch.zeros(1, 3, dtype=torch.float64, device="cuda")
     sdf = torch.empty(n, dtype=torch.float64, device="cuda")
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    st = _lib.stream_ptr()
     def go():
-        rc = L.dss_igr_query_list(ctypes.byref(net), ctypes.c_void_p(pts.data_ptr()), None, ctypes.c_void_p(lat.data_ptr()), 3, None, n, 2,
-                                  ctypes.c_void_p(sdf.data_ptr()), None, st)
+        rc = L.dss_igr_query_list(ctypes.byref(net), _lib.ptr(pts), None, _lib.ptr(lat), 3, None, n, 2, _lib.ptr(sdf), None, st)
         assert rc == 0, rc
     for _ in range(3): go()
     torch.cuda.synchronize()

@@ -3,8 +3,8 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes
 import numpy as np, torch
-from diffsdfsim_amd import _lib
-L = ctypes.CDLL(_lib.build(diag=True))
+from diffsdfsim_amd import _lib, world_abi
+L = world_abi.bind(ctypes.CDLL(_lib.build(diag=True)))
 names = ["dep fp64 fma", "4 indep fp64 fma chains (per 4)", "2 readlane + fma", "dep LDS read", "dep global read (L2)", "dep fp64 div", "dep fp64 sqrt+add", "dep shuffle+add"]
 n = 20000
 chase = torch.tensor((np.arange(1 << 16) * 37 + 11) & 0xFFFF, dtype=torch.int32, device="cuda")
@@ -14,7 +14,7 @@ for grid in (1, 1024, 4096):
     print("grid", grid)
     for mode, nm in enumerate(names):
         for _ in range(2):
-            L.dss_diag_latency(mode, n, grid, ctypes.c_void_p(sink.data_ptr()), ctypes.c_void_p(out.data_ptr()), None, ctypes.c_void_p(chase.data_ptr()), None)
+            L.dss_diag_latency(mode, n, grid, sink.data_ptr(), out.data_ptr(), None, chase.data_ptr(), None)
             torch.cuda.synchronize()
         o = out.cpu().numpy().reshape(grid, 2).astype(np.float64)
         cyc, wall = o[:, 0].mean(), o[:, 1].mean()

@@ -1,7 +1,6 @@
 """Diagnostic: phase shares of lcp_contact_forward_kernel (on the diagnostic build of the library, _lib.build(diag=True))."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import ctypes
 import numpy as np, torch
 from diffsdfsim_amd import _lib, scenes
 _lib.LIB_PATH = _lib.build(diag=True)
@@ -15,7 +14,7 @@ if KIND == "sphere":
 else:
     E = BatchEngine(scenes.box_stack(B, nbox=7, seed=1), maxc=128, max_cand=1024, max_pc=48, strict_no_pen=False, backend=TorchBackend("cuda"))
 st = torch.zeros(B * 16, dtype=torch.int64, device="cuda")
-E.be.lib.dss_diag_set_lcp_stamps(ctypes.c_void_p(st.data_ptr()), E.be.stream())
+E.be.lib.dss_diag_set_lcp_stamps(st.data_ptr(), E.be.stream())
 try:
     E.step()
 except RuntimeError as e:

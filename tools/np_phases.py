@@ -2,7 +2,6 @@
 build of the library, _lib.build(diag=True))."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import ctypes
 import numpy as np, torch
 from diffsdfsim_amd import _lib, scenes
 _lib.LIB_PATH = _lib.build(diag=True)
@@ -17,15 +16,13 @@ else:
     E = BatchEngine(spec, maxc=128, max_cand=1024, max_pc=48, strict_no_pen=False, backend=TorchBackend("cuda"))
 np_ = E.nb * (E.nb - 1)
 dbg = torch.zeros(B * np_ * 8, dtype=torch.int64, device="cuda")
-E.be.lib.dss_diag_set_np_stamps(ctypes.c_void_p(dbg.data_ptr()), E.be.stream())
+E.be.lib.dss_diag_set_np_stamps(dbg.data_ptr(), E.be.stream())
 E.step()
 torch.cuda.synchronize()
 d = dbg.cpu().numpy().reshape(B, np_, 8)
 names = ["scan", "fw", "project", "geom", "filter", "final"]
 act = d[:, :, 6] > 0
 print("active WGs per scene", act.sum() / B, "of", np_)
-for s_ in range(B):
-    pass
 dd = np.diff(d[:, :, :7], axis=2)[act] / 100.0   # us
 print("phase us mean:", dict(zip(names, dd.mean(0).round(1))), "total mean", dd.sum(1).mean().round(1), "max", dd.sum(1).max().round(1))
 a, b = np.nonzero(act)
