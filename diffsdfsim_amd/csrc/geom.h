@@ -567,6 +567,8 @@ template <class T> __host__ __device__ inline void igr_lin(const Shape<T> &s, in
 }
 #endif
 
+// the query cube [-s, s]^3 of a body of scale s
+__host__ __device__ inline bool in_cube(const double *p, double s) { return fabs(p[0]) <= s && fabs(p[1]) <= s && fabs(p[2]) <= s; }
 // SDF3D.query_sdfs: outside the [-scale, scale]^3 box: phi = scale, grad = 0
 template <class T> __host__ __device__ inline bool query_sdf(const Shape<T> &s, const T *pt, T &phi, T *g, bool want_grad)
 {

@@ -62,9 +62,8 @@ __global__ void __launch_bounds__(OV_NT) overlap_kernel(DssWorld W)
     if (tid < nb) s_igr[tid] = W.shape_type[(size_t)sc * nb + tid] == DSS_SHAPE_IGR;
 #endif
     for (int up = wv; up < nup; up += OV_NT / 64) {
-        int i = 0, rem = up;
-        while (rem >= nb - 1 - i) { rem -= nb - 1 - i; ++i; }
-        const int j = i + 1 + rem;
+        int i, j;
+        upair_of(up, nb, i, j);
         int ok = !W.no_contact[i * nb + j];
         if (ok) {
             BodyD A, Bd;
@@ -116,13 +115,12 @@ __global__ void __launch_bounds__(OV_NT) overlap_kernel(DssWorld W)
         int cnt[2] = {0, 0};
 #if DSS_ALL_SHAPES
         int nig = 0;
-        for (int up = 0, i = 0, j = 1; up < nup; ++up) {
+        for (int up = 0, i = 0, j = 1; up < nup; ++up, upair_next(nb, i, j)) {
             if (s_ok[up] && (s_igr[i] || s_igr[j])) nig += 2;
-            if (++j == nb) { ++i; j = i + 1; }
         }
         if (nig) {
             int at = atomicAdd(W.n_pairs + 6, nig);
-            for (int up = 0, i = 0, j = 1; up < nup; ++up) {
+            for (int up = 0, i = 0, j = 1; up < nup; ++up, upair_next(nb, i, j)) {
                 if (s_ok[up] && (s_igr[i] || s_igr[j])) {
                     s_ok[up] = 0;     // not an item of the analytic lists
                     if (W.igr_list && at + 2 <= W.igr_items_cap) {
@@ -130,26 +128,23 @@ __global__ void __launch_bounds__(OV_NT) overlap_kernel(DssWorld W)
                         W.igr_list[at++] = sc * np + j * (nb - 1) + i;
                     } else atomicOr(W.overflow + sc, 32);
                 }
-                if (++j == nb) { ++i; j = i + 1; }
             }
         }
 #endif
-        for (int up = 0, i = 0, j = 1; up < nup; ++up) {
+        for (int up = 0, i = 0, j = 1; up < nup; ++up, upair_next(nb, i, j)) {
             if (s_ok[up]) { ++cnt[s_big[i] ? 0 : 1]; ++cnt[s_big[j] ? 0 : 1]; }
-            if (++j == nb) { ++i; j = i + 1; }
         }
         const int cap = W.B * np;
         // both list lengths live in one 64-bit word (n_pairs[0], n_pairs[1]): one atomic per scene reserves both ranges
         const unsigned long long old = atomicAdd(reinterpret_cast<unsigned long long *>(W.n_pairs),
                                                  (unsigned long long)(unsigned)cnt[0] | ((unsigned long long)(unsigned)cnt[1] << 32));
         int at[2] = {(int)(old & 0xffffffffull), (int)(old >> 32)};
-        for (int up = 0, i = 0, j = 1; up < nup; ++up) {
+        for (int up = 0, i = 0, j = 1; up < nup; ++up, upair_next(nb, i, j)) {
             if (s_ok[up]) {
                 const int li = s_big[i] ? 0 : 1, lj = s_big[j] ? 0 : 1;
                 W.pair_list[(size_t)li * cap + at[li]++] = sc * np + i * (nb - 1) + (j - 1);
                 W.pair_list[(size_t)lj * cap + at[lj]++] = sc * np + j * (nb - 1) + i;
             }
-            if (++j == nb) { ++i; j = i + 1; }
         }
     }
 }
@@ -176,17 +171,11 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
     // not serialised behind the scratch stores
     const double *__restrict__ m_verts = W.verts, *__restrict__ m_fcent = W.fcent;
     const int *__restrict__ m_faces = W.faces;
-#define CB(f, k) cb[(size_t)(f) * MC + (k)]
     const double sB = Bd.g.shape.scale;
 
     // composite transform for the cheap centroid cull (pose-invariant centroids / radii)
-    double Ra[9], Rb[9], R12[9], t12[3];
-    quat_to_mat(A.g.q, Ra);
-    quat_to_mat(Bd.g.q, Rb);
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) R12[3 * i + j] = Rb[i] * Ra[j] + Rb[3 + i] * Ra[3 + j] + Rb[6 + i] * Ra[6 + j];
-        t12[i] = Rb[i] * (A.g.pos[0] - Bd.g.pos[0]) + Rb[3 + i] * (A.g.pos[1] - Bd.g.pos[1]) + Rb[6 + i] * (A.g.pos[2] - Bd.g.pos[2]);
-    }
+    double R12[9], t12[3];
+    pair_transform(A.g, Bd.g, R12, t12);
 
     // ---- 1. candidate faces (contacts.py:44-52) in ascending face order ------------------------
     // Runs of 256 faces whose culling box misses b's query cube are skipped outright.  Pass A tests the
@@ -200,12 +189,7 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
     constexpr int RUN = 256;   // faces per culling box (engine.mesh_table CHUNK)
     const int nch = (A.nf + RUN - 1) / RUN, lane = tid & 63, wv = tid >> 6;
     // cheap pre-test: the face centroid (pose-invariant, composite transform) lies in b's query cube (+ margin)
-    auto cull_face = [&](const double *c) -> int {
-        double cb2[3];
-        for (int i = 0; i < 3; ++i) cb2[i] = R12[3 * i] * c[0] + R12[3 * i + 1] * c[1] + R12[3 * i + 2] * c[2] + t12[i];
-        const double lim = sB + 1e-9 * (1.0 + sB);
-        return fabs(cb2[0]) <= lim && fabs(cb2[1]) <= lim && fabs(cb2[2]) <= lim;
-    };
+    auto cull_face = [&](const double *c) -> int { return centroid_in_cube(R12, t12, c, sB); };
     // the reference's candidate test (contacts.py:44-52) in its own order of operations
     // (split in two so that the loads of two faces can be in flight before either is tested)
     auto load_tri = [&](int f, double tri[3][3]) {
@@ -216,24 +200,14 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
         }
     };
     auto test_tri = [&](double tri[3][3], double pqr[3][3]) -> int {
-        double x[3] = {0, 0, 0};
-        for (int k = 0; k < 3; ++k) {
-            to_frame(A.g, Bd.g, tri[k], pqr[k]);
-            for (int i = 0; i < 3; ++i) x[i] += pqr[k][i];
-        }
-        div3(x, 3.0, x);   // the three exact quotients by one denominator (geom.h)
-        double phi, g[3], rad = 0.0;
+        double x[3], rad, phi, g[3];
+        face_in_frame(A.g, Bd.g, tri[0], tri[1], tri[2], pqr, x, rad);
         // the reference also asks for |grad phi| > 1e-12.  The box gradient is a unit vector wherever the query cube
         // is hit (outside: normalised max(q,0); inside/on the surface: the failsafe direction has norm >= 1) and zero
         // outside the cube, so for boxes that test is the cube test and the gradient need not be evaluated.
         const bool box = Bd.g.shape.type == SHAPE_BOX;
-        const bool in_cube = query_sdf(Bd.g.shape, x, phi, g, !box);
-        for (int k = 0; k < 3; ++k) {
-            const double d[3] = {x[0] - pqr[k][0], x[1] - pqr[k][1], x[2] - pqr[k][2]};
-            const double r = t_sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-            if (r > rad) rad = r;
-        }
-        if (box) return (phi < rad + W.eps) && in_cube;
+        const bool inside = query_sdf(Bd.g.shape, x, phi, g, !box);
+        if (box) return (phi < rad + W.eps) && inside;
         const double gn = t_sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
         return (phi < rad + W.eps) && (gn > 1e-12);
     };
@@ -248,29 +222,12 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
     if (G::BT == 64) {
         // one wavefront: (a) centroid pre-test of the runs that can hold a candidate, four independent loads in
         // flight, survivors packed in ascending order into LDS; (b) the full test on dense lanes.
-        // A run is also dropped if b's surface is out of reach of every face in it: b's SDF is an exact distance (1-Lipschitz),
-        // the run's box holds every face's bounding sphere, so phi_b(centroid) >= phi_b(box centre) - |half diagonal| and
-        // rad <= the smallest half extent, and a face with phi_b >= rad + eps is no candidate (contacts.py:52).  A level-set
-        // body's whole mesh lies in the query cube of a floor it is nowhere near.
-        auto run_far = [&](const double *bx) -> bool {
-#if DSS_ALL_SHAPES
-            if (Bd.g.shape.type == SHAPE_GRID || Bd.g.shape.type == SHAPE_BOWL || Bd.g.shape.type == SHAPE_IGR) return false;
-#endif
-            double m[3], e2 = 0.0, emin = INFINITY;
-            for (int i = 0; i < 3; ++i) {
-                m[i] = 0.5 * (bx[i] + bx[3 + i]);
-                const double e = 0.5 * (bx[3 + i] - bx[i]);
-                e2 += e * e; emin = fmin(emin, e);
-            }
-            double pu[3], u, gdum[3];
-            for (int i = 0; i < 3; ++i) pu[i] = (R12[3 * i] * m[0] + R12[3 * i + 1] * m[1] + R12[3 * i + 2] * m[2] + t12[i]) / sB;
-            sdf_unit(Bd.g.shape, pu, u, gdum, false);
-            return u * sB - sqrt(e2) >= emin + W.eps + 1e-9 * (1.0 + sB);
-        };
+        // A run is also dropped if b's surface is out of reach of every face in it (run_out_of_reach).
         int npass = 0;
         for (int base = 0; base < nch; base += G::BT) {
             const int ch = base + tid;
-            const int hit = ch < nch && box_hits(reg, fbox + (size_t)ch * 6) && !run_far(fbox + (size_t)ch * 6);
+            const int hit = ch < nch && box_hits(reg, fbox + (size_t)ch * 6) &&
+                            !run_out_of_reach(Bd.g.shape, R12, t12, sB, fbox + (size_t)ch * 6, W.eps);
             const int slot = compact_slot(hit, npass, S);
             if (slot >= 0 && slot < G::HCAP) S.hidx[slot] = ch;
         }
@@ -293,14 +250,14 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
                 const int slotA = compact_slot(flagA, ncand, S);
                 if (slotA >= 0 && slotA < MC) {
                     cface[slotA] = fA;
-                    for (int k = 0; k < 3; ++k) for (int i2 = 0; i2 < 3; ++i2) CB(3 * k + i2, slotA) = pqr[k][i2];
+                    for (int k = 0; k < 3; ++k) for (int i2 = 0; i2 < 3; ++i2) CB(F_PQR + 3 * k + i2, slotA) = pqr[k][i2];
                 }
                 if (base + 64 >= nsurv) break;
                 const int flagB = test_tri(triB, pqr) && vB;
                 const int slotB = compact_slot(flagB, ncand, S);
                 if (slotB >= 0 && slotB < MC) {
                     cface[slotB] = fB;
-                    for (int k = 0; k < 3; ++k) for (int i2 = 0; i2 < 3; ++i2) CB(3 * k + i2, slotB) = pqr[k][i2];
+                    for (int k = 0; k < 3; ++k) for (int i2 = 0; i2 < 3; ++i2) CB(F_PQR + 3 * k + i2, slotB) = pqr[k][i2];
                 }
             }
             G::sync();
@@ -369,7 +326,7 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
                     double pqr[3][3];
                     test_face(f, pqr);
                     cface[slot] = f;
-                    for (int k = 0; k < 3; ++k) for (int i2 = 0; i2 < 3; ++i2) CB(3 * k + i2, slot) = pqr[k][i2];
+                    for (int k = 0; k < 3; ++k) for (int i2 = 0; i2 < 3; ++i2) CB(F_PQR + 3 * k + i2, slot) = pqr[k][i2];
                 }
         if (ncand > MC) { over |= 1; ncand = MC; }
         if (tid == 0) { W.pc_stats[((size_t)sc * np + dp) * 2] = npass; W.pc_stats[((size_t)sc * np + dp) * 2 + 1] = ncand; }
@@ -384,7 +341,7 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
             const int slot = compact_slot(flag, ncand, S);
             if (slot >= 0 && slot < MC) {
                 cface[slot] = f;
-                for (int k = 0; k < 3; ++k) for (int i = 0; i < 3; ++i) CB(3 * k + i, slot) = pqr[k][i];
+                for (int k = 0; k < 3; ++k) for (int i = 0; i < 3; ++i) CB(F_PQR + 3 * k + i, slot) = pqr[k][i];
             }
             if (ncand > MC) { over |= 1; ncand = MC; }
         }
@@ -397,43 +354,22 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
     // The first candidate of every thread lives in registers for the whole loop (typical pairs have fewer
     // candidates than threads); further ones stream through the L2-resident scratch.  One barrier per
     // iteration: the two early-exit votes travel as ballots through a parity-double-buffered LDS word.
-    struct Cand { double pqr[9], x[3], abc[3]; };
-    // vertex bi of the triangle, picked with selects: a run-time index would push the struct into scratch memory
-    auto vtx = [](const Cand &c, int bi, int i) { return bi == 0 ? c.pqr[i] : (bi == 1 ? c.pqr[3 + i] : c.pqr[6 + i]); };
     auto load_c = [&](Cand &c, int k) {
-        for (int i = 0; i < 9; ++i) c.pqr[i] = CB(i, k);
-        for (int i = 0; i < 3; ++i) { c.x[i] = CB(9 + i, k); c.abc[i] = CB(12 + i, k); }
+        for (int i = 0; i < 9; ++i) c.pqr[i] = CB(F_PQR + i, k);
+        for (int i = 0; i < 3; ++i) { c.x[i] = CB(F_X + i, k); c.abc[i] = CB(F_ABC + i, k); }
     };
     auto store_c = [&](const Cand &c, int k) {
-        for (int i = 0; i < 3; ++i) { CB(9 + i, k) = c.x[i]; CB(12 + i, k) = c.abc[i]; }
+        for (int i = 0; i < 3; ++i) { CB(F_X + i, k) = c.x[i]; CB(F_ABC + i, k) = c.abc[i]; }
     };
     auto init_c = [&](Cand &c) {
-        double best = INFINITY; int bi = 0;
-        for (int v = 0; v < 3; ++v) {
-            double phi, g[3];
-            query_sdf(Bd.g.shape, c.pqr + 3 * v, phi, g, false);
-            if (phi < best) { best = phi; bi = v; }
-        }
-        for (int i = 0; i < 3; ++i) { c.x[i] = vtx(c, bi, i); c.abc[i] = (i == bi) ? 1.0 : 0.0; }
+        double phi[3], g[3];
+        for (int v = 0; v < 3; ++v) query_sdf(Bd.g.shape, c.pqr + 3 * v, phi[v], g, false);
+        fw_start(c, phi[0], phi[1], phi[2]);
     };
-    // NOTE the reference forms gamma as python_float * bool_tensor (contacts.py:72-73), which torch
-    // promotes to float32: the step sizes, and 1 - gamma, are float32-rounded.  Replicated bit for bit.
     auto eval_c = [&](const Cand &c, int iter, float &gm, int &bi, int &pen) {
         double phi, g[3];
         query_sdf(Bd.g.shape, c.x, phi, g, true);
-        double bestd = INFINITY; bi = 0;
-        for (int v = 0; v < 3; ++v) {
-            const double d = c.pqr[3 * v] * g[0] + c.pqr[3 * v + 1] * g[1] + c.pqr[3 * v + 2] * g[2];
-            if (d < bestd) { bestd = d; bi = v; }
-        }
-        const double impr = (c.x[0] - vtx(c, bi, 0)) * g[0] + (c.x[1] - vtx(c, bi, 1)) * g[1] + (c.x[2] - vtx(c, bi, 2)) * g[2];
-        gm = (fabs(impr) > W.tol) ? (float)(2.0 / (iter + 2.0)) : 0.0f;
-        pen = phi < -W.tol;
-    };
-    auto apply_c = [&](Cand &c, float g32, int bi) {
-        const double gm = (double)g32, om = (double)(1.0f - g32);
-        for (int i = 0; i < 3; ++i) { c.x[i] = om * c.x[i] + gm * vtx(c, bi, i); c.abc[i] *= om; }
-        for (int i = 0; i < 3; ++i) if (i == bi) c.abc[i] += gm;
+        fw_eval(c, phi, g, iter, W.tol, gm, bi, pen);
     };
     // iteration 0 for everybody; afterwards only candidates that still move are touched: a candidate whose
     // |improvement| <= tol keeps x, so every later evaluation repeats the same numbers and gamma stays 0
@@ -448,9 +384,9 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
             if (k < ncand) {
                 Cand c; load_c(c, k); init_c(c);
                 eval_c(c, 0, gm, bi, pen);
-                if (gm != 0.0f && !pen) apply_c(c, gm, bi);   // applied only if the loop is not left (decided below)
+                if (gm != 0.0f && !pen) fw_apply(c, gm, bi);   // applied only if the loop is not left (decided below)
                 store_c(c, k);
-                CB(25, k) = (double)gm; cstate[k] = bi;
+                CB(F_GAMMA, k) = (double)gm; cstate[k] = bi;
             }
             const unsigned long long bm = __ballot(gm != 0.0f), bp = __ballot(pen);
             if ((tid & 63) == 0) S.vote[0][tid >> 6] = (bm != 0ull ? 1 : 0) | (bp != 0ull ? 2 : 0);
@@ -463,7 +399,7 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
         if (vote & 2) {
             // a penetrating point in iteration 0: the reference leaves the loop BEFORE the update; undo it
             for (int k = tid; k < ncand; k += G::BT) {
-                const float gm = (float)CB(25, k);
+                const float gm = (float)CB(F_GAMMA, k);
                 if (gm != 0.0f) { Cand c; load_c(c, k); init_c(c); store_c(c, k); }
             }
             nmov = 0;
@@ -484,7 +420,7 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
         if (alive) load_c(m0, k0);
         for (int iter = 1; iter < 32; iter += 2) {
             Cand e = m0;
-            if (role) apply_c(e, (float)(2.0 / (iter + 2.0)), role - 1);
+            if (role) fw_apply(e, (float)(2.0 / (iter + 2.0)), role - 1);
             float gm = 0.0f; int bi = 0, pen = 0;
             if (alive) eval_c(e, role ? iter + 1 : iter, gm, bi, pen);
             // iteration `iter`: what role 0 found at the current point
@@ -493,7 +429,7 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
             const unsigned long long bmA = __ballot(alive && gmA != 0.0f), bpA = __ballot(alive && penA);
             if (gmA == 0.0f) alive = 0;                      // froze: x no longer changes
             if (bmA == 0ull || bpA != 0ull) break;           // all gamma == 0, or a penetrating point (contacts.py:74-77)
-            if (alive) apply_c(m0, gmA, biA);
+            if (alive) fw_apply(m0, gmA, biA);
             if (iter + 1 >= 32) break;
             // iteration `iter + 1`: what the lane that evaluated the point just moved to found there
             const int src = qbase + 1 + biA;
@@ -502,7 +438,7 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
             const unsigned long long bmB = __ballot(alive && gmB != 0.0f), bpB = __ballot(alive && penB);
             if (gmB == 0.0f) alive = 0;
             if (bmB == 0ull || bpB != 0ull) break;
-            if (alive) apply_c(m0, gmB, biB);
+            if (alive) fw_apply(m0, gmB, biB);
         }
         if (k0 >= 0 && role == 0) store_c(m0, k0);
         nmov = 0;     // the general loop below has nothing left to do
@@ -536,12 +472,12 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
         int vote = 0;
         for (int w = 0; w < G::BT / 64; ++w) vote |= S.vote[iter & 1][w];
         if (!(vote & 1) || (vote & 2)) break;   // all gamma == 0, or a penetrating point (contacts.py:74-77)
-        if (gam[0] != 0.0f) apply_c(m0, gam[0], ind[0]);
+        if (gam[0] != 0.0f) fw_apply(m0, gam[0], ind[0]);
         q = 1;
         for (int j = tid + G::BT; j < nmov; j += G::BT, ++q) {
             if (gam[q] == 0.0f) continue;
             const int k = S.hidx[j];
-            Cand c; load_c(c, k); apply_c(c, gam[q], ind[q]); store_c(c, k);
+            Cand c; load_c(c, k); fw_apply(c, gam[q], ind[q]); store_c(c, k);
         }
     }
     if (k0 >= 0) store_c(m0, k0);
@@ -568,14 +504,14 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
             const int *fv = m_faces + (size_t)(A.foff + f) * 3;
             double tri[3][3], xb1[3] = {0, 0, 0};
             for (int v = 0; v < 3; ++v) {
-                abc[v] = CB(12 + v, k);
+                abc[v] = CB(F_ABC + v, k);
                 const double *vp = m_verts + (size_t)(A.voff + fv[v]) * 3;
                 for (int i = 0; i < 3; ++i) { tri[v][i] = vp[i]; xb1[i] += tri[v][i] * abc[v]; }
             }
             double phi1, g1[3], gr[3], x[3], phi2, g2[3];
             query_sdf(A.g.shape, xb1, phi1, g1, true);
             quat_apply(qrel, g1, gr);
-            for (int i = 0; i < 3; ++i) x[i] = CB(9 + i, k) - phi1 * gr[i];
+            for (int i = 0; i < 3; ++i) x[i] = CB(F_X + i, k) - phi1 * gr[i];
             query_sdf(Bd.g.shape, x, phi2, g2, false);
             flag = phi2 <= W.eps;
             if (flag) {
@@ -589,10 +525,10 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
         const int slot = compact_slot(flag, ncon, S);
         if (slot >= 0) {
             kface[slot] = kf;
-            for (int i = 0; i < 3; ++i) {   // (slot <= k: fields 0-8, pqr, and 15-24 of a slot are dead or unread by now)
-                CB(15 + i, slot) = abc[i]; CB(18 + i, slot) = n[i]; CB(21 + i, slot) = p1[i]; CB(i, slot) = p2[i];
+            for (int i = 0; i < 3; ++i) {   // (slot <= k: F_PQR and the contact fields of a slot are dead or unread by now)
+                CB(F_CABC + i, slot) = abc[i]; CB(F_NORMAL + i, slot) = n[i]; CB(F_P1 + i, slot) = p1[i]; CB(F_P2 + i, slot) = p2[i];
             }
-            CB(24, slot) = pen;
+            CB(F_PEN, slot) = pen;
             // filter state of the contact (np_filter_emit.inc, NP_PRESTATE): 255 = no usable normal
             if (slot < G::HCAP) S.cst[slot] = t_sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]) > 1e-12 ? 0 : 255;
         }
@@ -613,7 +549,6 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
 #define NP_PRESTATE 1
 #include "np_filter_emit.inc"
 #undef NP_PRESTATE
-#undef CB
 }
 
 // persistent: groups pull items off the active-pair lists through shared cursors so that the long items (a 176 k-face
@@ -678,9 +613,8 @@ __global__ void __launch_bounds__(64) compact_contacts_kernel(DssWorld W, int *n
         const int slot = base + lane;
         int cnt = 0, a = 0, b = 0;
         if (slot < np) {
-            int i = 0, rem = slot >> 1;
-            while (rem >= nb - 1 - i) { rem -= nb - 1 - i; ++i; }
-            const int j = i + 1 + rem;
+            int i, j;
+            upair_of(slot >> 1, nb, i, j);
             a = (slot & 1) ? j : i; b = (slot & 1) ? i : j;
             cnt = W.pc_count[(size_t)sc * np + a * (nb - 1) + (b < a ? b : b - 1)];
         }

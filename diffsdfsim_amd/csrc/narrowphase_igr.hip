@@ -20,6 +20,10 @@
 //   G1-G4  contact geometry: Newton step on a, phi/grad of both bodies, the twelve Laplacian probes           contacts.py:161-214
 //   then the thinning and output stages shared with narrowphase.hip (np_common.h)                           contacts.py:97-158
 //
+// Only the control flow is this file's own.  The arithmetic of the search -- a face in b's frame, the cheap tests before it,
+// the start vertex, one Frank-Wolfe evaluation and update -- and the layout of the candidate scratch are those of
+// narrowphase.hip, from the same definitions in np_common.h.
+//
 // A pair whose bodies are both analytic never comes here; a stage whose query body is analytic evaluates it in place and
 // falls through to the next stage.  Query slots are reserved with one atomic per item and list; results depend on the
 // point alone, so the order in which items reserve is immaterial and the contact sets are deterministic.
@@ -33,10 +37,6 @@ using G = BlockGroup;
 enum { ST_SCAN = 0, ST_CAND, ST_INIT, ST_FW, ST_PROJ, ST_PROJ2, ST_PROJ3, ST_G2, ST_G3, ST_G4, ST_DONE };
 enum { H_STATE = 0, H_NCAND, H_NCON, H_ITER, H_OVER, H_QV, H_QG };
 enum { L_VALUE = 0, L_GRAD = 1 };
-
-#define CB(f, k) cb[(size_t)(f) * MC + (k)]
-
-__device__ inline bool in_cube(const double *p, double s) { return fabs(p[0]) <= s && fabs(p[1]) <= s && fabs(p[2]) <= s; }
 
 // the two query lists of one round
 struct Lists {
@@ -97,28 +97,6 @@ __device__ inline void take_grad(const Lists &L, int idx, const double *pt, doub
     normalize(raw, g);      // F.normalize(grads_ov) (bodies.py:741)
 }
 
-struct Cand { double pqr[9], x[3], abc[3]; };
-__device__ inline double vtx(const Cand &c, int bi, int i) { return bi == 0 ? c.pqr[i] : (bi == 1 ? c.pqr[3 + i] : c.pqr[6 + i]); }
-// one Frank-Wolfe evaluation (contacts.py:64-73) from phi, grad at the current point.  gamma is python_float * bool_tensor,
-// which torch promotes to float32: replicated (see narrowphase.hip)
-__device__ inline void fw_eval(const Cand &c, double phi, const double *g, int iter, double tol, float &gm, int &bi, int &pen)
-{
-    double bestd = INFINITY; bi = 0;
-    for (int v = 0; v < 3; ++v) {
-        const double d = c.pqr[3 * v] * g[0] + c.pqr[3 * v + 1] * g[1] + c.pqr[3 * v + 2] * g[2];
-        if (d < bestd) { bestd = d; bi = v; }
-    }
-    const double impr = (c.x[0] - vtx(c, bi, 0)) * g[0] + (c.x[1] - vtx(c, bi, 1)) * g[1] + (c.x[2] - vtx(c, bi, 2)) * g[2];
-    gm = (fabs(impr) > tol) ? (float)(2.0 / (iter + 2.0)) : 0.0f;
-    pen = phi < -tol;
-}
-__device__ inline void fw_apply(Cand &c, float g32, int bi)
-{
-    const double gm = (double)g32, om = (double)(1.0f - g32);
-    for (int i = 0; i < 3; ++i) { c.x[i] = om * c.x[i] + gm * vtx(c, bi, i); c.abc[i] *= om; }
-    for (int i = 0; i < 3; ++i) if (i == bi) c.abc[i] += gm;
-}
-
 __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, int last_round)
 {
     int *hdr = W.igr_hdr + (size_t)it * DSS_IGR_HDR;
@@ -148,11 +126,11 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
     G::sync();   // everybody has read the header before anybody rewrites it
 
     auto load_c = [&](Cand &c, int k) {
-        for (int i = 0; i < 9; ++i) c.pqr[i] = CB(i, k);
-        for (int i = 0; i < 3; ++i) { c.x[i] = CB(9 + i, k); c.abc[i] = CB(12 + i, k); }
+        for (int i = 0; i < 9; ++i) c.pqr[i] = CB(F_PQR + i, k);
+        for (int i = 0; i < 3; ++i) { c.x[i] = CB(F_X + i, k); c.abc[i] = CB(F_ABC + i, k); }
     };
     auto store_c = [&](const Cand &c, int k) {
-        for (int i = 0; i < 3; ++i) { CB(9 + i, k) = c.x[i]; CB(12 + i, k) = c.abc[i]; }
+        for (int i = 0; i < 3; ++i) { CB(F_X + i, k) = c.x[i]; CB(F_ABC + i, k) = c.abc[i]; }
     };
     // barycentric point of candidate / contact k on its triangle, in a's body frame
     auto bary_point = [&](int face, const double *abc, double *o) {
@@ -162,6 +140,12 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
             const double *vp = m_verts + (size_t)(A.voff + fv[v]) * 3;
             for (int i = 0; i < 3; ++i) o[i] += vp[i] * abc[v];
         }
+    };
+    // face f of a's mesh in b's frame: vertices, centroid, bounding radius (contacts.py:42-50)
+    auto face_vertices = [&](int f, double pqr[3][3], double *x, double &rad) {
+        const int *fv = m_faces + (size_t)(A.foff + f) * 3;
+        face_in_frame(A.g, Bd.g, m_verts + (size_t)(A.voff + fv[0]) * 3, m_verts + (size_t)(A.voff + fv[1]) * 3,
+                      m_verts + (size_t)(A.voff + fv[2]) * 3, pqr, x, rad);
     };
     auto finish = [&](int count) {      // the item ends with `count` contacts already written (0: none)
         if (tid == 0) { if (count >= 0) *pc_count = count; if (over) atomicOr(W.overflow + sc, over); }
@@ -173,65 +157,28 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
         switch (state) {
         case ST_SCAN: {
             // ---- candidate faces (contacts.py:44-52) in ascending face order ------------------------------------------
-            double Ra[9], Rb[9], R12[9], t12[3];
-            quat_to_mat(A.g.q, Ra);
-            quat_to_mat(Bd.g.q, Rb);
-            for (int i = 0; i < 3; ++i) {
-                for (int j = 0; j < 3; ++j) R12[3 * i + j] = Rb[i] * Ra[j] + Rb[3 + i] * Ra[3 + j] + Rb[6 + i] * Ra[6 + j];
-                t12[i] = Rb[i] * (A.g.pos[0] - Bd.g.pos[0]) + Rb[3 + i] * (A.g.pos[1] - Bd.g.pos[1]) + Rb[6 + i] * (A.g.pos[2] - Bd.g.pos[2]);
-            }
+            double R12[9], t12[3];
+            pair_transform(A.g, Bd.g, R12, t12);
             Region reg;
             region_of(A.g, Bd.g, 1e-9, reg);
             const double *fbox = W.fch_box + (size_t)W.mesh_fch_off[A.mesh] * 6;
             constexpr int RUN = 256;
             static_assert(RUN == G::BT, "one culling box per round of the group");
-            // the centroid, bounding radius and the reference's own candidate test of one face (contacts.py:42-52)
-            auto face_geom = [&](int f, double pqr[3][3], double *x, double &rad) {
-                const int *fv = m_faces + (size_t)(A.foff + f) * 3;
-                x[0] = x[1] = x[2] = 0.0; rad = 0.0;
-                for (int k = 0; k < 3; ++k) {
-                    to_frame(A.g, Bd.g, m_verts + (size_t)(A.voff + fv[k]) * 3, pqr[k]);
-                    for (int i = 0; i < 3; ++i) x[i] += pqr[k][i];
-                }
-                div3(x, 3.0, x);
-                for (int k = 0; k < 3; ++k) {
-                    const double d[3] = {x[0] - pqr[k][0], x[1] - pqr[k][1], x[2] - pqr[k][2]};
-                    const double r = t_sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-                    if (r > rad) rad = r;
-                }
-            };
             // b neural: every face whose centroid lies in b's query cube needs phi_b there before it can be judged.  Such
             // "tentative" faces can be many (all of a floor's faces under the body), so they live in the query list itself
             // (point + face id as the tag), not in the item's candidate scratch; two passes: count, then reserve and write.
-            // b analytic: the runs of 256 faces that can hold a candidate are listed first, one culling box per thread.  Beyond
-            // the query-cube test a run is dropped if b's surface is out of reach of every face in it: b's SDF is an exact
-            // distance (box / sphere / cylinder / ...: 1-Lipschitz), the run's box holds every face's bounding sphere, so
-            // phi_b(centroid) >= phi_b(box centre) - |half diagonal| and rad <= the smallest half extent; a face with
-            // phi_b >= rad + eps is no candidate (contacts.py:52).  A neural body's whole mesh lies in the query cube of a floor
-            // it is nowhere near -- 60 k faces read and tested per item and attempt, for nothing, without this.
+            // b analytic: the runs of 256 faces that can hold a candidate are listed first, one culling box per thread: those
+            // that pass the query-cube test and are not out of b's reach (run_out_of_reach).  A neural body's whole mesh lies in
+            // the query cube of a floor it is nowhere near -- 60 k faces read and tested per item and attempt, for nothing,
+            // without this.
             const int nch = (A.nf + RUN - 1) / RUN;
             int nrun = -1;
             if (!Bigr && nch <= G::HCAP) {
                 nrun = 0;
                 for (int cb0 = 0; cb0 < nch; cb0 += G::BT) {
                     const int ch = cb0 + tid;
-                    int keep = 0;
-                    if (ch < nch) {
-                        const double *bx = fbox + (size_t)ch * 6;
-                        keep = box_hits(reg, bx);
-                        if (keep && Bd.g.shape.type != SHAPE_GRID && Bd.g.shape.type != SHAPE_BOWL) {
-                            double m[3], e2 = 0.0, emin = INFINITY;
-                            for (int i = 0; i < 3; ++i) {
-                                m[i] = 0.5 * (bx[i] + bx[3 + i]);
-                                const double e = 0.5 * (bx[3 + i] - bx[i]);
-                                e2 += e * e; emin = fmin(emin, e);
-                            }
-                            double pu[3], u, gdum[3];
-                            for (int i = 0; i < 3; ++i) pu[i] = (R12[3 * i] * m[0] + R12[3 * i + 1] * m[1] + R12[3 * i + 2] * m[2] + t12[i]) / sB;
-                            sdf_unit(Bd.g.shape, pu, u, gdum, false);
-                            if (u * sB - sqrt(e2) >= emin + W.eps + 1e-9 * (1.0 + sB)) keep = 0;
-                        }
-                    }
+                    const double *bx = fbox + (size_t)ch * 6;
+                    const int keep = ch < nch && box_hits(reg, bx) && !run_out_of_reach(Bd.g.shape, R12, t12, sB, bx, W.eps);
                     const int slot = compact_slot(keep, nrun, S);
                     if (slot >= 0) S.hidx[slot] = ch;
                 }
@@ -248,12 +195,8 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                     double pqr[3][3], x[3] = {0, 0, 0}, rad = 0.0;
                     if (f < A.nf) {
                         // cheap pre-test: the pose-invariant centroid lies in b's query cube (+ margin)
-                        const double *c = m_fcent + (size_t)(A.foff + f) * 3;
-                        double c2[3];
-                        for (int i = 0; i < 3; ++i) c2[i] = R12[3 * i] * c[0] + R12[3 * i + 1] * c[1] + R12[3 * i + 2] * c[2] + t12[i];
-                        const double lim = sB + 1e-9 * (1.0 + sB);
-                        if (fabs(c2[0]) <= lim && fabs(c2[1]) <= lim && fabs(c2[2]) <= lim) {
-                            face_geom(f, pqr, x, rad);
+                        if (centroid_in_cube(R12, t12, m_fcent + (size_t)(A.foff + f) * 3, sB)) {
+                            face_vertices(f, pqr, x, rad);
                             if (Bigr) flag = in_cube(x, sB);        // outside: phi = scale, grad = 0 -> never a candidate
                             else {
                                 double phi, g[3];
@@ -269,7 +212,7 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                         if (pass == 1 && slot >= 0) { put(Q, L_VALUE, qv + slot, x, sB, latB); Q.tag[L_VALUE][qv + slot] = f; }
                     } else if (slot >= 0 && slot < MC) {
                         cface[slot] = f;
-                        for (int k = 0; k < 3; ++k) for (int i = 0; i < 3; ++i) CB(3 * k + i, slot) = pqr[k][i];
+                        for (int k = 0; k < 3; ++k) for (int i = 0; i < 3; ++i) CB(F_PQR + 3 * k + i, slot) = pqr[k][i];
                     }
                 }
                 G::sync();
@@ -291,13 +234,9 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                 // b analytic: the whole Frank-Wolfe search needs no network value
                 for (int k = tid; k < ncand; k += G::BT) {
                     Cand c; load_c(c, k);
-                    double best = INFINITY; int bi = 0;
-                    for (int v = 0; v < 3; ++v) {
-                        double phi, g[3];
-                        query_sdf(Bd.g.shape, c.pqr + 3 * v, phi, g, false);
-                        if (phi < best) { best = phi; bi = v; }
-                    }
-                    for (int i = 0; i < 3; ++i) { c.x[i] = vtx(c, bi, i); c.abc[i] = (i == bi) ? 1.0 : 0.0; }
+                    double phi[3], g[3];
+                    for (int v = 0; v < 3; ++v) query_sdf(Bd.g.shape, c.pqr + 3 * v, phi[v], g, false);
+                    fw_start(c, phi[0], phi[1], phi[2]);
                     store_c(c, k);
                     cstate[k] = 0;
                 }
@@ -316,7 +255,7 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                         query_sdf(Bd.g.shape, c.x, phi, g, true);
                         float gm; int bi, pen;
                         fw_eval(c, phi, g, itn, W.tol, gm, bi, pen);
-                        CB(25, k) = (double)gm; CB(26, k) = (double)bi;
+                        CB(F_GAMMA, k) = (double)gm; CB(F_VERT, k) = (double)bi;
                         moving |= gm != 0.0f; anyp |= pen;
                     }
                     const int mv = G::any(moving), pn = G::any(anyp);
@@ -324,9 +263,9 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                     for (int j = tid; j < nlist; j += G::BT) {
                         const int k = packed ? S.hidx[j] : j;
                         if (cstate[k] != 0) continue;
-                        const float gm = (float)CB(25, k);
+                        const float gm = (float)CB(F_GAMMA, k);
                         if (gm == 0.0f) { cstate[k] = -1; continue; }      // froze: x no longer changes
-                        Cand c; load_c(c, k); fw_apply(c, gm, (int)CB(26, k)); store_c(c, k);
+                        Cand c; load_c(c, k); fw_apply(c, gm, (int)CB(F_VERT, k)); store_c(c, k);
                     }
                     if (itn == 0) {
                         G::sync();
@@ -355,17 +294,7 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                 double pqr[3][3], x[3] = {0, 0, 0}, rad = 0.0;
                 if (k < nt) {
                     f = R.tag[L_VALUE][qv + k];
-                    const int *fv = m_faces + (size_t)(A.foff + f) * 3;
-                    for (int v = 0; v < 3; ++v) {       // the same arithmetic as in the scan: the same centroid, bit for bit
-                        to_frame(A.g, Bd.g, m_verts + (size_t)(A.voff + fv[v]) * 3, pqr[v]);
-                        for (int i = 0; i < 3; ++i) x[i] += pqr[v][i];
-                    }
-                    div3(x, 3.0, x);
-                    for (int v = 0; v < 3; ++v) {
-                        const double d[3] = {x[0] - pqr[v][0], x[1] - pqr[v][1], x[2] - pqr[v][2]};
-                        const double r = t_sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-                        if (r > rad) rad = r;
-                    }
+                    face_vertices(f, pqr, x, rad);       // the scan's centroid again, bit for bit: the value was asked for there
                     const double phi = take_value(R, L_VALUE, qv + k, x, sB);
                     flag = phi < rad + W.eps;
                 }
@@ -373,8 +302,8 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                 const int slot = compact_slot(flag, ncand, S);
                 if (slot >= 0 && slot < MC) {
                     cface[slot] = f;
-                    for (int v = 0; v < 3; ++v) for (int i = 0; i < 3; ++i) CB(3 * v + i, slot) = pqr[v][i];
-                    for (int i = 0; i < 3; ++i) CB(9 + i, slot) = x[i];
+                    for (int v = 0; v < 3; ++v) for (int i = 0; i < 3; ++i) CB(F_PQR + 3 * v + i, slot) = pqr[v][i];
+                    for (int i = 0; i < 3; ++i) CB(F_X + i, slot) = x[i];
                 }
             }
             if (ncand > MC) { over |= 1; ncand = MC; }
@@ -385,10 +314,10 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
             if (qv < 0 || qg < 0) { over |= 32; finish(0); break; }
             for (int k = tid; k < ncand; k += G::BT) {
                 double pt[3];
-                for (int i = 0; i < 3; ++i) pt[i] = CB(9 + i, k);
+                for (int i = 0; i < 3; ++i) pt[i] = CB(F_X + i, k);
                 put(Q, L_GRAD, qg + k, pt, sB, latB);                 // gradient at the centroid: the |grad| > 1e-12 test
                 for (int v = 0; v < 3; ++v) {
-                    for (int i = 0; i < 3; ++i) pt[i] = CB(3 * v + i, k);
+                    for (int i = 0; i < 3; ++i) pt[i] = CB(F_PQR + 3 * v + i, k);
                     put(Q, L_VALUE, qv + 3 * k + v, pt, sB, latB);
                 }
             }
@@ -402,12 +331,9 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                 double phc, gc[3];
                 take_grad(R, qg + k, c.x, sB, phc, gc);
                 const double gn = t_sqrt(gc[0] * gc[0] + gc[1] * gc[1] + gc[2] * gc[2]);
-                double best = INFINITY; int bi = 0;
-                for (int v = 0; v < 3; ++v) {
-                    const double phi = take_value(R, L_VALUE, qv + 3 * k + v, c.pqr + 3 * v, sB);
-                    if (phi < best) { best = phi; bi = v; }
-                }
-                for (int i = 0; i < 3; ++i) { c.x[i] = vtx(c, bi, i); c.abc[i] = (i == bi) ? 1.0 : 0.0; }
+                double phi[3];
+                for (int v = 0; v < 3; ++v) phi[v] = take_value(R, L_VALUE, qv + 3 * k + v, c.pqr + 3 * v, sB);
+                fw_start(c, phi[0], phi[1], phi[2]);
                 store_c(c, k);
                 cstate[k] = gn > 1e-12 ? 0 : -3;      // -3: not a candidate after all (cand_mask, contacts.py:52)
                 qrank[k] = k;
@@ -416,7 +342,7 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
             qg = reserve(Q, L_GRAD, ncand, S);
             if (qg < 0) { over |= 32; finish(0); break; }
             for (int k = tid; k < ncand; k += G::BT) {
-                const double x[3] = {CB(9, k), CB(10, k), CB(11, k)};
+                const double x[3] = {CB(F_X, k), CB(F_X + 1, k), CB(F_X + 2, k)};
                 put(Q, L_GRAD, qg + k, x, sB, latB);
             }
             iter = 0;
@@ -433,16 +359,16 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                 take_grad(R, qg + qrank[k], c.x, sB, phi, g);
                 float gm; int bi, pen;
                 fw_eval(c, phi, g, iter, W.tol, gm, bi, pen);
-                CB(25, k) = (double)gm; CB(26, k) = (double)bi;
+                CB(F_GAMMA, k) = (double)gm; CB(F_VERT, k) = (double)bi;
                 moving |= gm != 0.0f; anyp |= pen;
             }
             const int mv = G::any(moving), pn = G::any(anyp);
             if (!mv || pn) { state = ST_PROJ; break; }
             for (int k = tid; k < ncand; k += G::BT) {
                 if (cstate[k] != 0) continue;
-                const float gm = (float)CB(25, k);
+                const float gm = (float)CB(F_GAMMA, k);
                 if (gm == 0.0f) { cstate[k] = -1; continue; }
-                Cand c; load_c(c, k); fw_apply(c, gm, (int)CB(26, k)); store_c(c, k);
+                Cand c; load_c(c, k); fw_apply(c, gm, (int)CB(F_VERT, k)); store_c(c, k);
             }
             G::sync();
             if (++iter >= 32) { state = ST_PROJ; break; }
@@ -458,7 +384,7 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
             if (qg < 0) { over |= 32; finish(0); break; }
             for (int k = tid; k < ncand; k += G::BT) {
                 if (cstate[k] != 0) continue;
-                const double x[3] = {CB(9, k), CB(10, k), CB(11, k)};
+                const double x[3] = {CB(F_X, k), CB(F_X + 1, k), CB(F_X + 2, k)};
                 put(Q, L_GRAD, qg + qrank[k], x, sB, latB);
             }
             wait = true;
@@ -470,7 +396,7 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                 qg = reserve(Q, L_GRAD, ncand, S);
                 if (qg < 0) { over |= 32; finish(0); break; }
                 for (int k = tid; k < ncand; k += G::BT) {
-                    const double abc[3] = {CB(12, k), CB(13, k), CB(14, k)};
+                    const double abc[3] = {CB(F_ABC, k), CB(F_ABC + 1, k), CB(F_ABC + 2, k)};
                     double xb1[3];
                     bary_point(cface[k], abc, xb1);
                     put(Q, L_GRAD, qg + k, xb1, sA, latA);
@@ -485,20 +411,20 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
             quat_inv(Bd.g.q, qbi);
             quat_mul(qbi, A.g.q, qrel);
             for (int k = tid; k < ncand; k += G::BT) {
-                const double abc[3] = {CB(12, k), CB(13, k), CB(14, k)};
+                const double abc[3] = {CB(F_ABC, k), CB(F_ABC + 1, k), CB(F_ABC + 2, k)};
                 double xb1[3], phi1, g1[3], gr[3];
                 bary_point(cface[k], abc, xb1);
                 if (Aigr) take_grad(R, qg + k, xb1, sA, phi1, g1);
                 else query_sdf(A.g.shape, xb1, phi1, g1, true);
                 quat_apply(qrel, g1, gr);
-                for (int i = 0; i < 3; ++i) CB(9 + i, k) = CB(9 + i, k) - phi1 * gr[i];
+                for (int i = 0; i < 3; ++i) CB(F_X + i, k) = CB(F_X + i, k) - phi1 * gr[i];
             }
             G::sync();
             if (Bigr) {
                 qv = reserve(Q, L_VALUE, ncand, S);
                 if (qv < 0) { over |= 32; finish(0); break; }
                 for (int k = tid; k < ncand; k += G::BT) {
-                    const double x[3] = {CB(9, k), CB(10, k), CB(11, k)};
+                    const double x[3] = {CB(F_X, k), CB(F_X + 1, k), CB(F_X + 2, k)};
                     put(Q, L_VALUE, qv + k, x, sB, latB);
                 }
                 wait = true;
@@ -514,17 +440,17 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                 int flag = 0, f = 0;
                 double abc[3] = {0, 0, 0};
                 if (k < ncand && cstate[k] != -3) {
-                    const double x[3] = {CB(9, k), CB(10, k), CB(11, k)};
+                    const double x[3] = {CB(F_X, k), CB(F_X + 1, k), CB(F_X + 2, k)};
                     double phi2, g2[3];
                     if (Bigr) phi2 = take_value(R, L_VALUE, qv + k, x, sB);
                     else query_sdf(Bd.g.shape, x, phi2, g2, false);
                     flag = phi2 <= W.eps;
                     f = cface[k];
-                    for (int i = 0; i < 3; ++i) abc[i] = CB(12 + i, k);
+                    for (int i = 0; i < 3; ++i) abc[i] = CB(F_ABC + i, k);
                 }
                 if (!G::any(flag)) continue;
                 const int slot = compact_slot(flag, ncon, S);
-                if (slot >= 0) { kface[slot] = f; for (int i = 0; i < 3; ++i) CB(15 + i, slot) = abc[i]; }
+                if (slot >= 0) { kface[slot] = f; for (int i = 0; i < 3; ++i) CB(F_CABC + i, slot) = abc[i]; }
             }
             G::sync();
             if (ncon == 0) { finish(0); break; }
@@ -532,7 +458,7 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                 qg = reserve(Q, L_GRAD, ncon, S);
                 if (qg < 0) { over |= 32; finish(0); break; }
                 for (int j = tid; j < ncon; j += G::BT) {
-                    const double abc[3] = {CB(15, j), CB(16, j), CB(17, j)};
+                    const double abc[3] = {CB(F_CABC, j), CB(F_CABC + 1, j), CB(F_CABC + 2, j)};
                     double cp1[3];
                     bary_point(kface[j], abc, cp1);
                     put(Q, L_GRAD, qg + j, cp1, sA, latA);
@@ -545,7 +471,7 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
         case ST_G2: {
             // ---- Newton step onto a's surface (contacts.py:165-171), the point in b's frame (:173-179) -----------------
             for (int j = tid; j < ncon; j += G::BT) {
-                const double abc[3] = {CB(15, j), CB(16, j), CB(17, j)};
+                const double abc[3] = {CB(F_CABC, j), CB(F_CABC + 1, j), CB(F_CABC + 2, j)};
                 double cp1[3], d1, n1[3], p1[3], rel[3], cp2[3];
                 bary_point(kface[j], abc, cp1);
                 if (Aigr) take_grad(R, qg + j, cp1, sA, d1, n1);
@@ -554,13 +480,13 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                 quat_apply(A.g.q, cp1, p1);
                 for (int i = 0; i < 3; ++i) rel[i] = (p1[i] + A.g.pos[i]) - Bd.g.pos[i];
                 quat_apply_inv(Bd.g.q, rel, cp2);
-                for (int i = 0; i < 3; ++i) { CB(3 + i, j) = cp1[i]; CB(6 + i, j) = cp2[i]; }
+                for (int i = 0; i < 3; ++i) { CB(F_CP1 + i, j) = cp1[i]; CB(F_CP2 + i, j) = cp2[i]; }
             }
             G::sync();
             qg = reserve(Q, L_GRAD, nq * ncon, S);
             if (qg < 0) { over |= 32; finish(0); break; }
             for (int j = tid; j < ncon; j += G::BT) {
-                const double cp1[3] = {CB(3, j), CB(4, j), CB(5, j)}, cp2[3] = {CB(6, j), CB(7, j), CB(8, j)};
+                const double cp1[3] = {CB(F_CP1, j), CB(F_CP1 + 1, j), CB(F_CP1 + 2, j)}, cp2[3] = {CB(F_CP2, j), CB(F_CP2 + 1, j), CB(F_CP2 + 2, j)};
                 if (Aigr) put(Q, L_GRAD, qg + nq * j, cp1, sA, latA);
                 if (Bigr) put(Q, L_GRAD, qg + nq * j + (Aigr ? 1 : 0), cp2, sB, latB);
             }
@@ -570,23 +496,24 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
         case ST_G3: {
             // ---- phi, normal of both bodies at the contact point; the Laplacian probes (contacts.py:171-196) ------------
             for (int j = tid; j < ncon; j += G::BT) {
-                const double cp1[3] = {CB(3, j), CB(4, j), CB(5, j)}, cp2[3] = {CB(6, j), CB(7, j), CB(8, j)};
+                const double cp1[3] = {CB(F_CP1, j), CB(F_CP1 + 1, j), CB(F_CP1 + 2, j)}, cp2[3] = {CB(F_CP2, j), CB(F_CP2 + 1, j), CB(F_CP2 + 2, j)};
                 double d1, n1[3], d2, n2[3];
                 if (Aigr) take_grad(R, qg + nq * j, cp1, sA, d1, n1);
                 else query_sdf(A.g.shape, cp1, d1, n1, true);
                 if (Bigr) take_grad(R, qg + nq * j + (Aigr ? 1 : 0), cp2, sB, d2, n2);
                 else query_sdf(Bd.g.shape, cp2, d2, n2, true);
-                for (int i = 0; i < 3; ++i) { CB(9 + i, j) = n1[i]; CB(12 + i, j) = n2[i]; }
-                CB(25, j) = d1; CB(26, j) = d2;
+                for (int i = 0; i < 3; ++i) { CB(F_N1 + i, j) = n1[i]; CB(F_N2 + i, j) = n2[i]; }
+                CB(F_D1, j) = d1; CB(F_D2, j) = d2;
             }
             G::sync();
             qv = reserve(Q, L_VALUE, 6 * nq * ncon, S);
             if (qv < 0) { over |= 32; finish(0); break; }
             for (int j = tid; j < ncon; j += G::BT) {
+                static_assert(F_CP2 == F_CP1 + 3, "body 1's point follows body 0's");
                 int o = qv + 6 * nq * j;
                 for (int body = 0; body < 2; ++body) {
                     if (!(body == 0 ? Aigr : Bigr)) continue;
-                    double pt[3] = {CB(3 + 3 * body, j), CB(4 + 3 * body, j), CB(5 + 3 * body, j)};
+                    double pt[3] = {CB(F_CP1 + 3 * body, j), CB(F_CP1 + 3 * body + 1, j), CB(F_CP1 + 3 * body + 2, j)};
                     for (int i = 0; i < 3; ++i) {
                         const double save = pt[i];
                         pt[i] = save + 1e-3; put(Q, L_VALUE, o++, pt, body == 0 ? sA : sB, body == 0 ? latA : latB);
@@ -602,9 +529,9 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
             // ---- which body's normal (contacts.py:184-202), contact points, penetration (:204-209) ----------------------
             int bad = 0;
             for (int j = tid; j < ncon; j += G::BT) {
-                const double cp1[3] = {CB(3, j), CB(4, j), CB(5, j)}, cp2[3] = {CB(6, j), CB(7, j), CB(8, j)};
-                const double n1[3] = {CB(9, j), CB(10, j), CB(11, j)}, n2[3] = {CB(12, j), CB(13, j), CB(14, j)};
-                const double d1 = CB(25, j), d2 = CB(26, j);
+                const double cp1[3] = {CB(F_CP1, j), CB(F_CP1 + 1, j), CB(F_CP1 + 2, j)}, cp2[3] = {CB(F_CP2, j), CB(F_CP2 + 1, j), CB(F_CP2 + 2, j)};
+                const double n1[3] = {CB(F_N1, j), CB(F_N1 + 1, j), CB(F_N1 + 2, j)}, n2[3] = {CB(F_N2, j), CB(F_N2 + 1, j), CB(F_N2 + 2, j)};
+                const double d1 = CB(F_D1, j), d2 = CB(F_D2, j);
                 double lap[2];
                 int o = qv + 6 * nq * j;
                 for (int body = 0; body < 2; ++body) {
@@ -630,8 +557,8 @@ __device__ void advance(const DssWorld &W, ScratchT<G> &S, int it, int round, in
                 quat_apply(Bd.g.q, t, p2);
                 quat_apply(A.g.q, cp1, p1);
                 const double pen = -d2;
-                for (int i = 0; i < 3; ++i) { CB(18 + i, j) = n[i]; CB(21 + i, j) = p1[i]; CB(i, j) = p2[i]; }
-                CB(24, j) = pen;
+                for (int i = 0; i < 3; ++i) { CB(F_NORMAL + i, j) = n[i]; CB(F_P1 + i, j) = p1[i]; CB(F_P2 + i, j) = p2[i]; }
+                CB(F_PEN, j) = pen;
                 if (!(pen <= W.tol)) bad = 1;
             }
             if (G::any(bad)) {

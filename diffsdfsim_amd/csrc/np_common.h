@@ -1,6 +1,9 @@
 // np_common.h -- building blocks shared by the narrow-phase translation units (narrowphase.hip in its lean and full
-// compilation, narrowphase_igr.hip): work-item geometry, group-wide scans and reductions, the hull of a normal cluster
-// (contacts.py:126-152) and the last two stages of a work item -- thinning (contacts.py:97-158) and output.
+// compilation, narrowphase_igr.hip): work-item geometry (pair indices, the pair's transform, a face in b's frame and the
+// cheap tests that come before it), the layout of the candidate scratch (CandField, CB), the arithmetic of the Frank-Wolfe
+// search (contacts.py:39-94: Cand, fw_start, fw_eval, fw_apply -- stated once, both narrow phases are held to the reference
+// bit for bit), group-wide scans and reductions, the hull of a normal cluster (contacts.py:126-152) and the last two stages
+// of a work item -- thinning (contacts.py:97-158) and output.
 // Everything sits in the including file's anonymous namespace; DSS_ALL_SHAPES must be defined before inclusion.
 #pragma once
 #include <math.h>
@@ -31,6 +34,15 @@ __device__ inline void pair_of(int dp, int nb, int &a, int &b)
     const int r = dp % (nb - 1);
     b = r < a ? r : r + 1;
 }
+// undirected pair `up` (i < j, ascending: the callback order) -> (i, j); and the step to pair up + 1
+__device__ inline void upair_of(int up, int nb, int &i, int &j)
+{
+    i = 0;
+    int rem = up;
+    while (rem >= nb - 1 - i) { rem -= nb - 1 - i; ++i; }
+    j = i + 1 + rem;
+}
+__device__ inline void upair_next(int nb, int &i, int &j) { if (++j == nb) { ++i; j = i + 1; } }
 
 struct BodyD {
     BodyG<double> g;
@@ -104,6 +116,121 @@ __device__ inline bool box_hits(const Region &r, const double *bx)
     for (int i = 0; i < 3; ++i)
         if (bx[i] > r.c[i] + r.e[i] || bx[3 + i] < r.c[i] - r.e[i]) return false;
     return true;
+}
+// composite transform of the pair, a's frame -> b's frame: R12 = R_b^T R_a, t12 = R_b^T (x_a - x_b).  For the cheap tests on
+// pose-invariant mesh data (face centroids, culling boxes) only; a candidate's own points go through to_frame
+__device__ inline void pair_transform(const BodyG<double> &a, const BodyG<double> &b, double *R12, double *t12)
+{
+    double Ra[9], Rb[9];
+    quat_to_mat(a.q, Ra);
+    quat_to_mat(b.q, Rb);
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) R12[3 * i + j] = Rb[i] * Ra[j] + Rb[3 + i] * Ra[3 + j] + Rb[6 + i] * Ra[6 + j];
+        t12[i] = Rb[i] * (a.pos[0] - b.pos[0]) + Rb[3 + i] * (a.pos[1] - b.pos[1]) + Rb[6 + i] * (a.pos[2] - b.pos[2]);
+    }
+}
+// cheap pre-test of a face: its centroid c (a's frame) lies in b's query cube [-sB, sB]^3 (+ margin)
+__device__ inline int centroid_in_cube(const double *R12, const double *t12, const double *c, double sB)
+{
+    double c2[3];
+    for (int i = 0; i < 3; ++i) c2[i] = R12[3 * i] * c[0] + R12[3 * i + 1] * c[1] + R12[3 * i + 2] * c[2] + t12[i];
+    const double lim = sB + 1e-9 * (1.0 + sB);
+    return fabs(c2[0]) <= lim && fabs(c2[1]) <= lim && fabs(c2[2]) <= lim;
+}
+// A run of 256 faces (culling box bx, a's frame) whose query-cube test passed is still dropped if b's surface is out of reach
+// of every face in it: b's SDF is an exact distance (box / sphere / cylinder / ...: 1-Lipschitz), the run's box holds every
+// face's bounding sphere, so phi_b(centroid) >= phi_b(box centre) - |half diagonal| and rad <= the smallest half extent, and
+// a face with phi_b >= rad + eps is no candidate (contacts.py:52).  A level-set or neural body's whole mesh lies in the
+// query cube of a floor it is nowhere near.  Never for a b whose SDF is no such distance (grid, bowl) or costs a network
+// evaluation (neural).
+__device__ inline bool run_out_of_reach(const Shape<double> &shape_b, const double *R12, const double *t12, double sB,
+                                        const double *bx, double eps)
+{
+#if DSS_ALL_SHAPES
+    if (shape_b.type == SHAPE_GRID || shape_b.type == SHAPE_BOWL || shape_b.type == SHAPE_IGR) return false;
+#endif
+    double m[3], e2 = 0.0, emin = INFINITY;
+    for (int i = 0; i < 3; ++i) {
+        m[i] = 0.5 * (bx[i] + bx[3 + i]);
+        const double e = 0.5 * (bx[3 + i] - bx[i]);
+        e2 += e * e; emin = fmin(emin, e);
+    }
+    double pu[3], u, gdum[3];
+    for (int i = 0; i < 3; ++i) pu[i] = (R12[3 * i] * m[0] + R12[3 * i + 1] * m[1] + R12[3 * i + 2] * m[2] + t12[i]) / sB;
+    sdf_unit(shape_b, pu, u, gdum, false);
+    return u * sB - sqrt(e2) >= emin + eps + 1e-9 * (1.0 + sB);
+}
+// A face of a's mesh in b's frame (contacts.py:42-50): its vertices v0, v1, v2 (a's frame) -> pqr, their centroid x (three
+// exact quotients by one denominator, geom.h) and the radius of the bounding sphere around it
+__device__ inline void face_in_frame(const BodyG<double> &a, const BodyG<double> &b, const double *v0, const double *v1,
+                                     const double *v2, double pqr[3][3], double *x, double &rad)
+{
+    to_frame(a, b, v0, pqr[0]);
+    to_frame(a, b, v1, pqr[1]);
+    to_frame(a, b, v2, pqr[2]);
+    x[0] = x[1] = x[2] = 0.0; rad = 0.0;
+    for (int k = 0; k < 3; ++k)
+        for (int i = 0; i < 3; ++i) x[i] += pqr[k][i];
+    div3(x, 3.0, x);
+    for (int k = 0; k < 3; ++k) {
+        const double d[3] = {x[0] - pqr[k][0], x[1] - pqr[k][1], x[2] - pqr[k][2]};
+        const double r = t_sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        if (r > rad) rad = r;
+    }
+}
+
+// ---- candidate scratch ------------------------------------------------------------------------
+// A slot of the candidate scratch is DSS_CAND_FIELDS rows of MC doubles, cb[field][k].  A row means one thing while the
+// slot is a CANDIDATE of the Frank-Wolfe search (stages 1-3) and another once it is a CONTACT (stages 4-6); contacts are
+// compacted to slots <= their candidate's, and a stage only overwrites rows that are dead or unread by then.
+#define CB(f, k) cb[(size_t)(f) * MC + (k)]
+enum CandField {
+    // search: the triangle in b's frame (vertex-major), the current point, its barycentrics, and the pending update of an
+    // iteration -- step size (a float32 value) and arg-min vertex (narrowphase.hip keeps the vertex in cstate instead)
+    F_PQR = 0, F_X = 9, F_ABC = 12, F_GAMMA = 25, F_VERT = 26,
+    // contact: world-frame point on b, barycentrics of the kept candidate, normal, point on a, penetration
+    F_P2 = 0, F_CABC = 15, F_NORMAL = 18, F_P1 = 21, F_PEN = 24,
+    // the neural path's geometry stages G2-G4, between the two: contact point in a's and in b's frame, both bodies'
+    // normals and distances there
+    F_CP1 = 3, F_CP2 = 6, F_N1 = 9, F_N2 = 12, F_D1 = 25, F_D2 = 26,
+    // the hull of a cluster beyond the LDS scratch (HullGlobal, after the contact geometry): points and keep-flags
+    F_HULL_P = 3, F_HULL_FLAG = 6,
+    F_SPARE = 27, F_COUNT
+};
+static_assert(F_COUNT == DSS_CAND_FIELDS, "the candidate scratch is allocated with DSS_CAND_FIELDS rows per slot");
+
+// ---- the Frank-Wolfe search of one candidate (contacts.py:57-82) ---------------------------------------------------------
+// The arithmetic both narrow phases are held to, bit for bit: what differs between them is where phi and its gradient
+// come from (an analytic query in place, or a network round) and how the candidates are walked.
+struct Cand { double pqr[9], x[3], abc[3]; };
+// vertex bi of the triangle, picked with selects: a run-time index would push the struct into scratch memory
+__device__ inline double vtx(const Cand &c, int bi, int i) { return bi == 0 ? c.pqr[i] : (bi == 1 ? c.pqr[3 + i] : c.pqr[6 + i]); }
+// start vertex = arg min of phi_b over the three vertices, the first on ties (contacts.py:57-61)
+__device__ inline void fw_start(Cand &c, double phi0, double phi1, double phi2)
+{
+    const double phi[3] = {phi0, phi1, phi2};
+    double best = INFINITY; int bi = 0;
+    for (int v = 0; v < 3; ++v) if (phi[v] < best) { best = phi[v]; bi = v; }
+    for (int i = 0; i < 3; ++i) { c.x[i] = vtx(c, bi, i); c.abc[i] = (i == bi) ? 1.0 : 0.0; }
+}
+// one evaluation (contacts.py:64-73) from phi, grad at the current point.  The reference forms gamma as
+// python_float * bool_tensor, which torch promotes to float32: the step sizes, and 1 - gamma, are float32-rounded.
+__device__ inline void fw_eval(const Cand &c, double phi, const double *g, int iter, double tol, float &gm, int &bi, int &pen)
+{
+    double bestd = INFINITY; bi = 0;
+    for (int v = 0; v < 3; ++v) {
+        const double d = c.pqr[3 * v] * g[0] + c.pqr[3 * v + 1] * g[1] + c.pqr[3 * v + 2] * g[2];
+        if (d < bestd) { bestd = d; bi = v; }
+    }
+    const double impr = (c.x[0] - vtx(c, bi, 0)) * g[0] + (c.x[1] - vtx(c, bi, 1)) * g[1] + (c.x[2] - vtx(c, bi, 2)) * g[2];
+    gm = (fabs(impr) > tol) ? (float)(2.0 / (iter + 2.0)) : 0.0f;
+    pen = phi < -tol;
+}
+__device__ inline void fw_apply(Cand &c, float g32, int bi)
+{
+    const double gm = (double)g32, om = (double)(1.0f - g32);
+    for (int i = 0; i < 3; ++i) { c.x[i] = om * c.x[i] + gm * vtx(c, bi, i); c.abc[i] *= om; }
+    for (int i = 0; i < 3; ++i) if (i == bi) c.abc[i] += gm;
 }
 
 // ---- workgroup scratch ------------------------------------------------------------------------
@@ -207,7 +334,7 @@ template <class G> __device__ inline double block_sum(double v, ScratchT<G> &S)
 // flat drop the coordinate of least variance and retry in 2-D; then 1-D min/max.
 // where a cluster's points and keep-flags live while its hull is taken: in LDS (clusters of up to HCAP points) or, for the
 // clusters a level-set mesh resting flat on a neighbour produces (every face of the resting side), in the group's global
-// candidate scratch (rows 3-6 of cand_buf, dead after the contact geometry stage)
+// candidate scratch (rows F_HULL_P, F_HULL_FLAG of cand_buf, dead after the contact geometry stage)
 template <class G> struct HullLds {
     ScratchT<G> *S;
     __device__ inline double hp(int k, int d) const { return S->hp[3 * k + d]; }
@@ -216,9 +343,9 @@ template <class G> struct HullLds {
 };
 struct HullGlobal {
     double *cb; int mc;
-    __device__ inline double hp(int k, int d) const { return cb[(size_t)(3 + d) * mc + k]; }
-    __device__ inline int getf(int k) const { return (int)cb[(size_t)6 * mc + k]; }
-    __device__ inline void setf(int k, int v) const { cb[(size_t)6 * mc + k] = (double)v; }
+    __device__ inline double hp(int k, int d) const { return cb[(size_t)(F_HULL_P + d) * mc + k]; }
+    __device__ inline int getf(int k) const { return (int)cb[(size_t)F_HULL_FLAG * mc + k]; }
+    __device__ inline void setf(int k, int v) const { cb[(size_t)F_HULL_FLAG * mc + k] = (double)v; }
 };
 
 
@@ -767,21 +894,20 @@ __device__ __noinline__ void emit_unfiltered(const DssWorld &W, int sc, int dp, 
     for (int k = tid; k < nout; k += G::BT) {
         pf[k] = kface[k];
         for (int i = 0; i < 3; ++i) {
-            pabc[(size_t)i * MP + k] = cb[(size_t)(15 + i) * MC + k];
-            pg[(size_t)i * MP + k] = cb[(size_t)(18 + i) * MC + k];
-            pg[(size_t)(3 + i) * MP + k] = cb[(size_t)(21 + i) * MC + k];
-            pg[(size_t)(6 + i) * MP + k] = cb[(size_t)i * MC + k];
+            pabc[(size_t)i * MP + k] = CB(F_CABC + i, k);
+            pg[(size_t)i * MP + k] = CB(F_NORMAL + i, k);
+            pg[(size_t)(3 + i) * MP + k] = CB(F_P1 + i, k);
+            pg[(size_t)(6 + i) * MP + k] = CB(F_P2 + i, k);
         }
-        pg[(size_t)9 * MP + k] = cb[(size_t)24 * MC + k];
+        pg[(size_t)9 * MP + k] = CB(F_PEN, k);
     }
     if (tid == 0) { W.pc_count[(size_t)sc * np + dp] = -nout; if (over) atomicOr(W.overflow + sc, over); }
 }
 
 // ---- stages 5 and 6 of a work item: thin the contacts (greedy normal clusters, hull of each; contacts.py:97-158) and
 // write the kept ones, in ascending face order, to the pair's output slots.  On entry the candidate scratch holds, for
-// contacts k < ncon: kface[k], barycentrics (fields 15-17), normal (18-20), p1 (21-23), p2 (0-2), penetration (24).
+// contacts k < ncon: kface[k] and the contact fields of CandField.
 // Returns 1 if a wavefront-sized group has to hand the item to a workgroup, else 0.
-#define CB(f, k) cb[(size_t)(f) * MC + (k)]
 template <class G>
 __device__ __forceinline__ int filter_and_emit(const DssWorld &W, ScratchT<G> &S, int item, int sc, int dp, int ncon, int over,
                                                int *__restrict__ cface, int *__restrict__ kface, int *__restrict__ cstate,
@@ -791,6 +917,5 @@ __device__ __forceinline__ int filter_and_emit(const DssWorld &W, ScratchT<G> &S
     int *pc_count = W.pc_count + (size_t)sc * np + dp;
 #include "np_filter_emit.inc"
 }
-#undef CB
 
 }  // namespace

@@ -3,8 +3,8 @@
 // Included inside narrow_pair (narrowphase.hip; the lean kernel's register allocation depends on this code sitting in that
 // function as written) and as the body of filter_and_emit (np_common.h) for the round-based neural narrow phase.
 // Expects in scope: G, W, S, item, sc, np, dp, tid, ncon, over, cface, kface, cstate, cb + CB(f, k), MC, pc_count, STAMP(i) (np_common.h).
-// On entry the candidate scratch holds, for contacts k < ncon: kface[k], barycentrics (fields 15-17), normal (18-20),
-// p1 (21-23), p2 (0-2), penetration (24).
+// On entry the candidate scratch holds, for contacts k < ncon: kface[k] and the contact fields of CandField (np_common.h):
+// barycentrics, normal, p1, p2, penetration.
     STAMP(4);
     // ---- 5. filter: greedy normal clusters, hull of each (contacts.py:97-158) -------------------
     int nkeep = 0;
@@ -26,7 +26,7 @@
         if (!lds_state)
 #endif
         for (int k = tid; k < ncon; k += G::BT) {
-            const double nn = t_sqrt(CB(18, k) * CB(18, k) + CB(19, k) * CB(19, k) + CB(20, k) * CB(20, k));
+            const double nn = t_sqrt(CB(F_NORMAL, k) * CB(F_NORMAL, k) + CB(F_NORMAL + 1, k) * CB(F_NORMAL + 1, k) + CB(F_NORMAL + 2, k) * CB(F_NORMAL + 2, k));
             set_state(k, nn > 1e-12 ? 0 : 255);
         }
         G::sync();
@@ -35,7 +35,7 @@
             for (int k = tid; k < ncon; k += G::BT) if (get_state(k) == 0) { mine = k; break; }
             const int seed = block_argmin(mine >= 0 ? (double)mine : INFINITY, mine, S);
             if (seed < 0) break;
-            const double sn[3] = {CB(18, seed), CB(19, seed), CB(20, seed)};
+            const double sn[3] = {CB(F_NORMAL, seed), CB(F_NORMAL + 1, seed), CB(F_NORMAL + 2, seed)};
             // gather the cluster (ascending) into the hull scratch
             int m = 0;
             for (int base = 0; base < ncon; base += G::BT) {
@@ -43,8 +43,8 @@
                 int in = 0;
                 double p1v[3] = {0.0, 0.0, 0.0};
                 if (k < ncon && get_state(k) == 0) {
-                    const double nk[3] = {CB(18, k), CB(19, k), CB(20, k)};
-                    for (int i = 0; i < 3; ++i) p1v[i] = CB(21 + i, k);
+                    const double nk[3] = {CB(F_NORMAL, k), CB(F_NORMAL + 1, k), CB(F_NORMAL + 2, k)};
+                    for (int i = 0; i < 3; ++i) p1v[i] = CB(F_P1 + i, k);
                     const double d = fmin(nk[0] * sn[0] + nk[1] * sn[1] + nk[2] * sn[2], 1.0);
                     // acos(d) < 1e-2 (contacts.py:112): decided by d against cos(1e-2) wherever that is safe (a margin of
                     // 1e-12 in d is 1e-10 rad, a million times acos' rounding); the arc cosine itself only in between
@@ -71,7 +71,7 @@
                     const int k = base + tid;
                     const int in = k < ncon && get_state(k) == 3;
                     const int slot = compact_slot(in, m, S);
-                    if (slot >= 0) { cface[slot] = k; for (int i = 0; i < 3; ++i) CB(3 + i, slot) = CB(21 + i, k); }
+                    if (slot >= 0) { cface[slot] = k; for (int i = 0; i < 3; ++i) CB(F_HULL_P + i, slot) = CB(F_P1 + i, k); }
                 }
                 G::sync();
                 const HullGlobal P{cb, MC};
@@ -116,8 +116,8 @@
     if (ncon <= 1) {
         if (tid == 0) {
             pf[0] = kface[0];
-            for (int i = 0; i < 3; ++i) { pabc[(size_t)i * MP] = CB(15 + i, 0); pg[(size_t)i * MP] = CB(18 + i, 0); pg[(size_t)(3 + i) * MP] = CB(21 + i, 0); pg[(size_t)(6 + i) * MP] = CB(i, 0); }
-            pg[(size_t)9 * MP] = CB(24, 0);
+            for (int i = 0; i < 3; ++i) { pabc[(size_t)i * MP] = CB(F_CABC + i, 0); pg[(size_t)i * MP] = CB(F_NORMAL + i, 0); pg[(size_t)(3 + i) * MP] = CB(F_P1 + i, 0); pg[(size_t)(6 + i) * MP] = CB(F_P2 + i, 0); }
+            pg[(size_t)9 * MP] = CB(F_PEN, 0);
         }
         nout = 1;
     } else {
@@ -135,10 +135,10 @@
             if (slot >= 0 && slot < MP) {
                 pf[slot] = kface[k];
                 for (int i = 0; i < 3; ++i) {
-                    pabc[(size_t)i * MP + slot] = CB(15 + i, k);
-                    pg[(size_t)i * MP + slot] = CB(18 + i, k); pg[(size_t)(3 + i) * MP + slot] = CB(21 + i, k); pg[(size_t)(6 + i) * MP + slot] = CB(i, k);
+                    pabc[(size_t)i * MP + slot] = CB(F_CABC + i, k);
+                    pg[(size_t)i * MP + slot] = CB(F_NORMAL + i, k); pg[(size_t)(3 + i) * MP + slot] = CB(F_P1 + i, k); pg[(size_t)(6 + i) * MP + slot] = CB(F_P2 + i, k);
                 }
-                pg[(size_t)9 * MP + slot] = CB(24, k);
+                pg[(size_t)9 * MP + slot] = CB(F_PEN, k);
             }
         }
         if (nout > MP) { over |= 4; nout = MP; }

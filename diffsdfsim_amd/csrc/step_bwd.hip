@@ -253,8 +253,6 @@ __device__ void contact_vjp(const DssWorld &W, int sc, const double *pose_n, int
 // (geom.h: igr_lin).  bwd_igr_prep_kernel lists those points for the sub-step every scene is about to undo -- body 1 at the
 // barycentric point of the contact's triangle, body 2 at the contact point in its frame -- igr_query_kernel evaluates the
 // list twice on the matrix cores (d/dxyz, d/dlatent), igr_records turns the answers into the records of one contact.
-__device__ inline bool in_cube3(const double *p, double s) { return fabs(p[0]) <= s && fabs(p[1]) <= s && fabs(p[2]) <= s; }
-
 __global__ void __launch_bounds__(64) bwd_igr_prep_kernel(DssWorld W_arg, DssAdjoint A_arg)
 {
     static_assert(sizeof(DssWorld) % 8 == 0, "the adjoint descriptor follows the world descriptor without padding");
@@ -288,7 +286,7 @@ __global__ void __launch_bounds__(64) bwd_igr_prep_kernel(DssWorld W_arg, DssAdj
                 for (int i = 0; i < 3; ++i) rel[i] = (v.geom_n[(size_t)(3 + i) * MX + c] + P1[4 + i]) - P2[4 + i];
                 quat_apply_inv(P2, rel, pt);
             }
-            if (!in_cube3(pt, scale)) { idx[side] = -2; continue; }       // query_sdfs: phi = scale, grad = 0 out there
+            if (!in_cube(pt, scale)) { idx[side] = -2; continue; }       // query_sdfs: phi = scale, grad = 0 out there
             const int slot = atomicAdd(A.igr_bw_n, 1);
             double u[3];
             div3(pt, scale, u);
