@@ -20,7 +20,10 @@
 //     are in flight.  Two workgroups' waves share a SIMD, so one's softplus epilogue (VALU) hides under the other's MFMAs.
 //   * the grid is persistent over the tiles of a point list whose length may live in device memory (the query rounds of
 //     the neural narrow phase, narrowphase_igr.hip, fill such lists); every point names its latent code by an index.
-// Flops: 4 x 115 456 MAC per point = 0.92 MFLOP (fp64) with tangents; matrix peak 256 CU x 128 flop/clk x 2.4 GHz = 78.6 TFLOP/s.
+//   * the same body is instantiated for the shapenet network (IGR_data/train_configs/shapenet.conf: latent 4, 8 x 256, skip into
+//     layer 4): input 7, 16 neuron tiles and 64 k-steps per layer, activations [16 NG rows][256+1].  A 4-number latent code has one
+//     tangent more than the tile holds, so d phi / d latent ([n][4]) takes two passes seeding latent coordinates 0-2 and 3.
+// Flops (128-wide): 4 x 115 456 MAC per point = 0.92 MFLOP (fp64) with tangents; matrix peak 256 CU x 128 flop/clk x 2.4 GHz = 78.6 TFLOP/s.
 // Measured (128^3 grid, MI355X): 38.0 ms = 50.9 TFLOP/s = 65 % of peak.
 #include <math.h>
 
@@ -32,7 +35,17 @@
 namespace {
 using namespace dss;
 
-constexpr int H = 128, NL = 9, DIN = 5, LDX = H + 1;
+constexpr int NL = 9;
+// A network shape the kernels are built for: hidden width H_ (H_/16 neuron tiles, H_/4 k-steps per layer) and latent size L_
+// (input = [latent(L_), xyz(3)]; layer 3 emits H_ - DIN rows, the skip concat appends the DIN inputs).
+template <int H_, int L_> struct Net {
+    static constexpr int H = H_, L = L_, DIN = L_ + 3, LDX = H_ + 1, TILES = H_ / 16, KS = H_ / 4;
+    // waves per SIMD the register allocation aims at (0 = the compiler's choice).  The 256-wide variants are workgroups of 8
+    // waves, two per SIMD: 3 waves per SIMD would leave a CU with ONE workgroup and nobody to hide its softplus epilogue.
+    static constexpr int WAVES_PER_SIMD = H_ > 128 ? 4 : 0;
+};
+using NetBobSpot = Net<128, 2>;    // IGR_data/train_configs/bob_spot_setup.conf:38-45
+using NetShapenet = Net<256, 4>;   // IGR_data/train_configs/shapenet.conf (can, mug, camera)
 enum { MODE_XYZ = DSS_IGR_XYZ, MODE_LATENT = DSS_IGR_LATENT, MODE_VALUE = DSS_IGR_VALUE };
 
 __device__ inline acc4 mfma(double a, double b, acc4 c) { return mfma_f64_16x16x4(a, b, c); }
@@ -96,22 +109,28 @@ __device__ inline void softplus100(double z, double &h, double &dh)
 struct Query {
     const double *pts;       // [n][3] points in the network's unit frame
     const int *lat_idx;      // [n] index of the point's latent code, or NULL = code 0
-    const double *latents;   // [.][lat_stride] latent codes (first two entries of a row)
+    const double *latents;   // [.][lat_stride] latent codes (first L entries of a row)
     int lat_stride;
+    int tan0;                // MODE_LATENT with L > 3: the latent coordinate of tangent 0 (the tile holds three tangents per pass)
     const int *n_dev;        // length of the list in device memory, or NULL = n
     int n;
-    double *sdf, *grad;      // [n], [n][3] (grad unused in MODE_VALUE)
+    double *sdf, *grad;      // [n], [n][3] (grad unused in MODE_VALUE; [n][L] in MODE_LATENT with L > 3)
 };
 
-// Wp: packed weights.  Per hidden->hidden layer (7 of them): [tile t 0..7][kstep 0..31][lane 0..63] = W[16t + (lane&15)][4ks + (lane>>4)]
-// NW waves per workgroup share the activations of NG row groups; wave w owns neuron tiles [w*8/NW, (w+1)*8/NW)
+// Wp: packed weights.  Per hidden->hidden layer (7 of them): [tile t 0..H/16-1][kstep 0..H/4-1][lane 0..63] = W[16t + (lane&15)][4ks + (lane>>4)]
+// NW waves per workgroup share the activations of NG row groups; wave w owns neuron tiles [w*TILES/NW, (w+1)*TILES/NW)
 // bid / nblk: this workgroup's place among the workgroups that walk Q's tiles (a launch may serve two lists, see below)
-template <int NW, int NG, int MODE> __device__ __forceinline__ void
+template <class NET, int NW, int NG, int MODE> __device__ __forceinline__ void
 igr_body(const Query &Q, int bid, int nblk, double *X, const double *W0, const double *b0, const double *Wp, const double *bh,
          const double *W8, const double *b8)
 {
     constexpr bool TAN = MODE != MODE_VALUE;
-    constexpr int PTS = (TAN ? 4 : 16) * NG, ROWS = 16 * NG, NT = 64 * NW, TPW = 8 / NW;
+    constexpr int H = NET::H, L = NET::L, DIN = NET::DIN, LDX = NET::LDX, TILES = NET::TILES, KS = NET::KS;
+    constexpr int PTS = (TAN ? 4 : 16) * NG, ROWS = 16 * NG, NT = 64 * NW, TPW = TILES / NW;
+    static_assert(TILES % NW == 0, "every wave owns the same number of neuron tiles");
+    // latent tangents: tangent d of this pass is latent coordinate t0 + d; the gradient row has GS entries
+    constexpr int GS = (MODE == MODE_LATENT && L > 3) ? L : 3;
+    const int t0 = (MODE == MODE_LATENT && L > 3) ? Q.tan0 : 0;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int col = lane & 15, q = lane >> 4;
     const int n = Q.n_dev ? *Q.n_dev : Q.n;
@@ -119,14 +138,14 @@ igr_body(const Query &Q, int bid, int nblk, double *X, const double *W0, const d
     auto row_of = [](int p, int quant) { return TAN ? 16 * (p / 4) + 4 * quant + (p % 4) : p; };
 
     for (int base = bid * PTS; base < n; base += nblk * PTS) {
-        // ---- layer 0 (K = 5) on the vector ALU: h0 = softplus(W0 [latent, xyz] + b0), tangents = sigma' * W0[:, seed]
+        // ---- layer 0 (K = DIN) on the vector ALU: h0 = softplus(W0 [latent, xyz] + b0), tangents = sigma' * W0[:, seed]
         for (int e = tid; e < PTS * H; e += NT) {
             const int p = e / H, j = e % H, gp = base + p;
-            double in[DIN] = {0.0, 0.0, 0.0, 0.0, 0.0};
+            double in[DIN] = {};
             if (gp < n) {
                 const double *lat = Q.latents + (size_t)(Q.lat_idx ? Q.lat_idx[gp] : 0) * Q.lat_stride;
-                in[0] = lat[0]; in[1] = lat[1];
-                in[2] = Q.pts[3 * gp]; in[3] = Q.pts[3 * gp + 1]; in[4] = Q.pts[3 * gp + 2];
+                for (int k = 0; k < L; ++k) in[k] = lat[k];
+                in[L] = Q.pts[3 * gp]; in[L + 1] = Q.pts[3 * gp + 1]; in[L + 2] = Q.pts[3 * gp + 2];
             }
             double z = b0[j];
             for (int k = 0; k < DIN; ++k) z += W0[j * DIN + k] * in[k];
@@ -134,17 +153,17 @@ igr_body(const Query &Q, int bid, int nblk, double *X, const double *W0, const d
             softplus100(z, h, dh);
             X[row_of(p, 0) * LDX + j] = h;
             if (TAN) {
-                // tangent seeds: the three point coordinates (inputs 2..4), or the two latent coordinates (inputs 0, 1)
+                // tangent seeds: the three point coordinates (inputs L..L+2), or latent coordinates t0..t0+2 (those below L)
                 for (int d = 0; d < 3; ++d)
-                    X[row_of(p, d + 1) * LDX + j] = MODE == MODE_LATENT ? (d < 2 ? dh * W0[j * DIN + d] : 0.0) : dh * W0[j * DIN + 2 + d];
+                    X[row_of(p, d + 1) * LDX + j] = MODE == MODE_LATENT ? (t0 + d < L ? dh * W0[j * DIN + t0 + d] : 0.0) : dh * W0[j * DIN + L + d];
             }
         }
         __syncthreads();
 
         for (int layer = 1; layer < NL - 1; ++layer) {
-            const double *Wl = Wp + (size_t)(layer - 1) * 8 * 32 * 64, *bl = bh + (size_t)(layer - 1) * H;
+            const double *Wl = Wp + (size_t)(layer - 1) * TILES * KS * 64, *bl = bh + (size_t)(layer - 1) * H;
             if (layer == 4) {
-                // skip connection: x = cat([h3 (123), input (5)]) / sqrt(2)   (value rows get the input, tangent rows its Jacobian)
+                // skip connection: x = cat([h3 (H - DIN), input (DIN)]) / sqrt(2)   (value rows get the input, tangent rows its Jacobian)
                 for (int e = tid; e < ROWS * H; e += NT) {
                     const int r = e / H, j = e % H;
                     double v = X[r * LDX + j];
@@ -155,11 +174,11 @@ igr_body(const Query &Q, int bid, int nblk, double *X, const double *W0, const d
                             v = 0.0;
                             if (gp < n) {
                                 const double *lat = Q.latents + (size_t)(Q.lat_idx ? Q.lat_idx[gp] : 0) * Q.lat_stride;
-                                v = k < 2 ? lat[k] : Q.pts[3 * gp + k - 2];
+                                v = k < L ? lat[k] : Q.pts[3 * gp + k - L];
                             }
                         } else {
                             const bool wl = MODE == MODE_LATENT;
-                            v = ((wl ? k : k - 2) == quant - 1 && (wl ? k < 2 : k >= 2)) ? 1.0 : 0.0;
+                            v = ((wl ? k - t0 : k - L) == quant - 1 && (wl ? k < L : k >= L)) ? 1.0 : 0.0;
                         }
                     }
                     X[r * LDX + j] = v * 0.70710678118654752440;
@@ -171,19 +190,19 @@ igr_body(const Query &Q, int bid, int nblk, double *X, const double *W0, const d
                 for (int t = 0; t < TPW; ++t) { comp(acc[g][t], 0) = 0; comp(acc[g][t], 1) = 0; comp(acc[g][t], 2) = 0; comp(acc[g][t], 3) = 0; }
             // software pipeline: the B fragments (and A) of k-step ks+1 are in flight while the MFMAs of ks issue
             double bq[2][TPW], aq[2][NG], bias[TPW];
-            const double *Ww = Wl + (size_t)wv * TPW * 32 * 64;
+            const double *Ww = Wl + (size_t)wv * TPW * KS * 64;
 #pragma unroll
             for (int t = 0; t < TPW; ++t) bias[t] = bl[16 * (wv * TPW + t) + col];
 #pragma unroll
-            for (int t = 0; t < TPW; ++t) bq[0][t] = Ww[(size_t)t * 32 * 64 + lane];
+            for (int t = 0; t < TPW; ++t) bq[0][t] = Ww[(size_t)t * KS * 64 + lane];
 #pragma unroll
             for (int g = 0; g < NG; ++g) aq[0][g] = X[(16 * g + col) * LDX + q];
 #pragma unroll
-            for (int ks = 0; ks < 32; ++ks) {
+            for (int ks = 0; ks < KS; ++ks) {
                 const int cur = ks & 1, nxt = cur ^ 1;
-                if (ks + 1 < 32) {
+                if (ks + 1 < KS) {
 #pragma unroll
-                    for (int t = 0; t < TPW; ++t) bq[nxt][t] = Ww[((size_t)t * 32 + ks + 1) * 64 + lane];
+                    for (int t = 0; t < TPW; ++t) bq[nxt][t] = Ww[((size_t)t * KS + ks + 1) * 64 + lane];
                     // A fragments: lane holds X[row = lane&15 (+16 g)][k = 4 ks + (lane>>4)]
 #pragma unroll
                     for (int g = 0; g < NG; ++g) aq[nxt][g] = X[(16 * g + col) * LDX + 4 * (ks + 1) + q];
@@ -222,17 +241,18 @@ igr_body(const Query &Q, int bid, int nblk, double *X, const double *W0, const d
             const int quant = TAN ? (r % 16) / 4 : 0, p = TAN ? 4 * (r / 16) + (r % 4) : r, gp = base + p;
             if (gp < n) {
                 if (quant == 0) Q.sdf[gp] = acc + b8[0];
-                else Q.grad[3 * gp + quant - 1] = acc;
+                else if constexpr (GS == 3) Q.grad[3 * gp + quant - 1] = acc;
+                else if (t0 + quant - 1 < GS) Q.grad[GS * gp + t0 + quant - 1] = acc;   // (the pass for coordinate 3 writes one column)
             }
         }
         __syncthreads();   // the next tile's layer 0 overwrites X
     }
 }
-template <int NW, int NG, int MODE> __global__ void __launch_bounds__(64 * NW)
+template <class NET, int NW, int NG, int MODE> __global__ void __launch_bounds__(64 * NW, NET::WAVES_PER_SIMD)
 igr_query_kernel(Query Q, const double *W0, const double *b0, const double *Wp, const double *bh, const double *W8, const double *b8)
 {
     DSS_DYN_LDS(double, X);   // [ROWS][LDX]; with tangents row = 16 g + 4*quantity + point, without row = point
-    igr_body<NW, NG, MODE>(Q, (int)blockIdx.x, (int)gridDim.x, X, W0, b0, Wp, bh, W8, b8);
+    igr_body<NET, NW, NG, MODE>(Q, (int)blockIdx.x, (int)gridDim.x, X, W0, b0, Wp, bh, W8, b8);
 }
 // One launch for the two lists of a query round of the neural narrow phase: workgroups [0, split) walk the value list, the
 // rest the gradient list.  Both lists are short most of the time (a Frank-Wolfe round: a few points per item), so each on
@@ -244,17 +264,17 @@ igr_query2_kernel(Query Qv, Query Qg, int split, const double *W0, const double 
 {
     DSS_DYN_LDS(double, X);
     const int bid = (int)blockIdx.x;
-    if (bid < split) igr_body<NW, NG, MODE_VALUE>(Qv, bid, split, X, W0, b0, Wp, bh, W8, b8);
-    else igr_body<NW, NG, MODE_XYZ>(Qg, bid - split, (int)gridDim.x - split, X, W0, b0, Wp, bh, W8, b8);
+    if (bid < split) igr_body<NetBobSpot, NW, NG, MODE_VALUE>(Qv, bid, split, X, W0, b0, Wp, bh, W8, b8);
+    else igr_body<NetBobSpot, NW, NG, MODE_XYZ>(Qg, bid - split, (int)gridDim.x - split, X, W0, b0, Wp, bh, W8, b8);
 }
 
-template <int NW, int NG, int MODE>
+template <class NET, int NW, int NG, int MODE>
 void launch(const Query &Q, const DssIgrNet &N, int n_cap, int est, hipStream_t stream)
 {
     constexpr int PTS = (MODE == MODE_VALUE ? 16 : 4) * NG;
-    const size_t lds = (size_t)16 * NG * LDX * sizeof(double);
+    const size_t lds = (size_t)16 * NG * NET::LDX * sizeof(double);
     if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute((const void *)igr_query_kernel<NW, NG, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void *)igr_query_kernel<NET, NW, NG, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     long tiles = ((long)n_cap + PTS - 1) / PTS;
     if (Q.n_dev) {
         // The length is only known on the device.  The grid is persistent over the tiles, so ANY size is correct; what it
@@ -270,7 +290,7 @@ void launch(const Query &Q, const DssIgrNet &N, int n_cap, int est, hipStream_t 
         if (tiles > cap) tiles = cap;
     }
     if (tiles < 1) tiles = 1;
-    hipLaunchKernelGGL((igr_query_kernel<NW, NG, MODE>), dim3((unsigned)tiles), dim3(64 * NW), lds, stream, Q, N.W0, N.b0, N.Wp,
+    hipLaunchKernelGGL((igr_query_kernel<NET, NW, NG, MODE>), dim3((unsigned)tiles), dim3(64 * NW), lds, stream, Q, N.W0, N.b0, N.Wp,
                        N.bh, N.W8, N.b8);
 }
 
@@ -285,7 +305,7 @@ template <int PTS> inline long tiles_for(int n_cap, int est)
 }
 template <int NW, int NG> void launch2(const Query &Qv, const Query &Qg, const DssIgrNet &N, int n_cap, int estv, int estg, hipStream_t stream)
 {
-    const size_t lds = (size_t)16 * NG * LDX * sizeof(double);
+    const size_t lds = (size_t)16 * NG * NetBobSpot::LDX * sizeof(double);
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute((const void *)igr_query2_kernel<NW, NG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const long tv = tiles_for<16 * NG>(n_cap, estv), tg = tiles_for<4 * NG>(n_cap, estg);
@@ -293,20 +313,53 @@ template <int NW, int NG> void launch2(const Query &Qv, const Query &Qg, const D
                        N.Wp, N.bh, N.W8, N.b8);
 }
 
-template <int MODE> void launch_mode(const Query &Q, const DssIgrNet &N, int n_cap, int est, hipStream_t stream)
+template <class NET, int MODE> struct Variants;
+template <int MODE> struct Variants<NetBobSpot, MODE> {
+    static void launch_mode(const Query &Q, const DssIgrNet &N, int n_cap, int est, hipStream_t stream)
+    {
+        // big batches (grid builds, the candidate rounds of a large scene batch): 4 waves share 2 row groups (32 KB of LDS: four
+        // workgroups per CU, so that one's softplus epilogue hides under another's MFMAs; measured 41.9 / 58.1 TFLOP/s without /
+        // with tangents against 39.7 / 57.8 for 4 row groups); small ones (a Frank-Wolfe round moves a few points per item): one row group per
+        // workgroup, a quarter of the latency of a pass and four times as many workgroups to spread over the chip.
+        // All variants give bit-identical results (a point's row never mixes with its tile-mates').
+        const int n = Q.n_dev ? (est < 0 ? n_cap : est) : n_cap;
+        if (n >= 16 * 1024) launch<NetBobSpot, 4, 2, MODE>(Q, N, n_cap, est, stream);
+        else if (n >= 2 * 1024) launch<NetBobSpot, 2, 2, MODE>(Q, N, n_cap, est, stream);
+        else launch<NetBobSpot, 4, 1, MODE>(Q, N, n_cap, est, stream);
+    }
+};
+template <int MODE> struct Variants<NetShapenet, MODE> {
+    static void launch_mode(const Query &Q, const DssIgrNet &N, int n_cap, int est, hipStream_t stream)
+    {
+        // 16 neuron tiles per layer: 8 waves keep a wave at the 2 tiles x NG row groups of accumulators that the 128-wide
+        // <4, NG> variants hold (NG * 16 / NW tiles per wave), so the register budget and the waves per SIMD carry over.
+        // LDS is 16 NG (256 + 1) 8 bytes: 64.25 KB for two row groups (two workgroups = 16 waves per CU of 160 KB, four per
+        // SIMD, the occupancy of the 128-wide <4, 2>), 32.1 KB for one (short lists: half the latency of a pass).  Four row
+        // groups would take 128.5 KB and leave a single workgroup per CU with nobody to hide its epilogue.  Not yet timed.
+        const int n = Q.n_dev ? (est < 0 ? n_cap : est) : n_cap;
+        if (n >= 2 * 1024) launch<NetShapenet, 8, 2, MODE>(Q, N, n_cap, est, stream);
+        else launch<NetShapenet, 8, 1, MODE>(Q, N, n_cap, est, stream);
+    }
+};
+template <class NET> void launch_net(Query Q, const DssIgrNet &N, int n_cap, int mode, int est, hipStream_t stream)
 {
-    // big batches (grid builds, the candidate rounds of a large scene batch): 4 waves share 2 row groups (32 KB of LDS: four
-    // workgroups per CU, so that one's softplus epilogue hides under another's MFMAs; measured 41.9 / 58.1 TFLOP/s without /
-    // with tangents against 39.7 / 57.8 for 4 row groups); small ones (a Frank-Wolfe round moves a few points per item): one row group per
-    // workgroup, a quarter of the latency of a pass and four times as many workgroups to spread over the chip.
-    // All variants give bit-identical results (a point's row never mixes with its tile-mates').
-    const int n = Q.n_dev ? (est < 0 ? n_cap : est) : n_cap;
-    if (n >= 16 * 1024) launch<4, 2, MODE>(Q, N, n_cap, est, stream);
-    else if (n >= 2 * 1024) launch<2, 2, MODE>(Q, N, n_cap, est, stream);
-    else launch<4, 1, MODE>(Q, N, n_cap, est, stream);
+    if (mode == MODE_VALUE) Variants<NET, MODE_VALUE>::launch_mode(Q, N, n_cap, est, stream);
+    else if (mode == MODE_XYZ) Variants<NET, MODE_XYZ>::launch_mode(Q, N, n_cap, est, stream);
+    else
+        // the tile has three tangents per point: latent coordinates 0-2, then (L = 4) a pass for coordinate 3
+        for (Q.tan0 = 0; Q.tan0 < NET::L; Q.tan0 += 3) Variants<NET, MODE_LATENT>::launch_mode(Q, N, n_cap, est, stream);
 }
 
-inline bool net_ok(const DssIgrNet *N) { return N && N->W0 && N->b0 && N->Wp && N->bh && N->W8 && N->b8; }
+// DssIgrNet.width / .latent -> the instantiation (0 = the 128 / 2 network); -1 = not built
+enum { NET_BOB_SPOT = 0, NET_SHAPENET = 1 };
+inline int net_kind(const DssIgrNet &N)
+{
+    const int w = N.width ? N.width : NetBobSpot::H, l = N.latent ? N.latent : NetBobSpot::L;
+    if (w == NetBobSpot::H && l == NetBobSpot::L) return NET_BOB_SPOT;
+    if (w == NetShapenet::H && l == NetShapenet::L) return NET_SHAPENET;
+    return -1;
+}
+inline bool net_ok(const DssIgrNet *N) { return N && N->W0 && N->b0 && N->Wp && N->bh && N->W8 && N->b8 && net_kind(*N) >= 0; }
 
 }  // namespace
 
@@ -315,10 +368,11 @@ namespace dss {
 int launch_igr_list(const DssIgrNet &N, const double *pts, const int *lat_idx, const double *latents, int lat_stride,
                     const int *n_dev, int n_cap, int mode, double *sdf, double *grad, hipStream_t stream, int est)
 {
-    Query Q{pts, lat_idx, latents, lat_stride, n_dev, n_cap, sdf, grad};
-    if (mode == MODE_VALUE) launch_mode<MODE_VALUE>(Q, N, n_cap, est, stream);
-    else if (mode == MODE_LATENT) launch_mode<MODE_LATENT>(Q, N, n_cap, est, stream);
-    else launch_mode<MODE_XYZ>(Q, N, n_cap, est, stream);
+    const Query Q{pts, lat_idx, latents, lat_stride, 0, n_dev, n_cap, sdf, grad};
+    const int kind = net_kind(N);
+    if (kind == NET_BOB_SPOT) launch_net<NetBobSpot>(Q, N, n_cap, mode, est, stream);
+    else if (kind == NET_SHAPENET) launch_net<NetShapenet>(Q, N, n_cap, mode, est, stream);
+    else return DSS_E_UNSUPPORTED;
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }
 // the value list and the gradient list of one query round in one launch (both lengths in device memory)
@@ -326,7 +380,9 @@ int launch_igr_pair(const DssIgrNet &N, const double *pts_v, const int *lat_v, c
                     const int *lat_g, const int *n_g, double *sdf_g, double *grad_g, const double *latents, int lat_stride, int n_cap,
                     hipStream_t stream, int est_v, int est_g)
 {
-    Query Qv{pts_v, lat_v, latents, lat_stride, n_v, n_cap, sdf_v, nullptr}, Qg{pts_g, lat_g, latents, lat_stride, n_g, n_cap, sdf_g, grad_g};
+    // (the stepper carries three shape parameters per body: its query rounds exist for the 128 / 2 network only)
+    if (net_kind(N) != NET_BOB_SPOT) return DSS_E_UNSUPPORTED;
+    Query Qv{pts_v, lat_v, latents, lat_stride, 0, n_v, n_cap, sdf_v, nullptr}, Qg{pts_g, lat_g, latents, lat_stride, 0, n_g, n_cap, sdf_g, grad_g};
     // variant by the work expected (a gradient point is four rows): see launch_mode
     const long rows = (est_v < 0 || est_g < 0) ? (long)n_cap : (long)est_v + 4L * est_g;
     if (rows >= 16 * 1024) launch2<4, 2>(Qv, Qg, N, n_cap, est_v, est_g, stream);
@@ -344,7 +400,7 @@ int dss_igr_query(const double *pts, const double *latent, const double *W0, con
                   const double *bh, const double *W8, const double *b8, int n, double *sdf, double *grad, void *stream)
 {
     if (!pts || !latent || !W0 || !b0 || !Wp || !bh || !W8 || !b8 || !sdf || !grad || n <= 0) return DSS_E_BADARG;
-    const DssIgrNet N{W0, b0, Wp, bh, W8, b8};
+    const DssIgrNet N{W0, b0, Wp, bh, W8, b8, 0, 0};
     return dss::launch_igr_list(N, pts, nullptr, latent, 2, nullptr, n, MODE_XYZ, sdf, grad, (hipStream_t)stream, -1);
 }
 
@@ -355,14 +411,14 @@ int dss_igr_query_latent_grad(const double *pts, const double *latent, const dou
                               const double *bh, const double *W8, const double *b8, int n, double *sdf, double *grad, void *stream)
 {
     if (!pts || !latent || !W0 || !b0 || !Wp || !bh || !W8 || !b8 || !sdf || !grad || n <= 0) return DSS_E_BADARG;
-    const DssIgrNet N{W0, b0, Wp, bh, W8, b8};
+    const DssIgrNet N{W0, b0, Wp, bh, W8, b8, 0, 0};
     return dss::launch_igr_list(N, pts, nullptr, latent, 2, nullptr, n, MODE_LATENT, sdf, grad, (hipStream_t)stream, -1);
 }
 
 int dss_igr_query_list(const DssIgrNet *net, const double *pts, const int *lat_idx, const double *latents, int lat_stride,
                        const int *n_dev, int n_cap, int mode, double *sdf, double *grad, void *stream)
 {
-    if (!net_ok(net) || !pts || !latents || !sdf || n_cap <= 0 || lat_stride < 2) return DSS_E_BADARG;
+    if (!net_ok(net) || !pts || !latents || !sdf || n_cap <= 0 || lat_stride < (net->latent ? net->latent : 2)) return DSS_E_BADARG;
     if (mode != MODE_VALUE && mode != MODE_XYZ && mode != MODE_LATENT) return DSS_E_BADARG;
     if (mode != MODE_VALUE && !grad) return DSS_E_BADARG;
     return dss::launch_igr_list(*net, pts, lat_idx, latents, lat_stride, n_dev, n_cap, mode, sdf, grad, (hipStream_t)stream, -1);

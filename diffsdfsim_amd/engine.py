@@ -148,7 +148,11 @@ class BatchEngine:
         for name, shp in shapes.items():
             self.arr[name] = self.be.zeros(shp, abi.NP_DTYPE[kinds[name]])
         if igr_b.any():
-            for k in abi.IGR_NET_FIELDS:
+            from . import igr
+            if igr.packed_shape(spec["igr_net"]) != igr.SHAPES[0]:
+                raise NotImplementedError("the stepper carries 3 shape parameters per body (shape_prm): its neural bodies use the "
+                                          "5 -> 8 x 128 -> 1 network with a 2-number latent code")
+            for k in abi.IGR_NET_POINTERS:
                 w = spec["igr_net"][k]
                 self.arr["igr_" + k] = w if not isinstance(w, np.ndarray) and hasattr(w, "data_ptr") else self.be.from_numpy(np.asarray(w, np.float64))
         host = dict(mt)

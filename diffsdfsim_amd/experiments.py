@@ -550,6 +550,8 @@ def main(argv=None):
     ap.add_argument("--scenes", type=int, default=64)
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--net", default="bob_spot", choices=["bob_spot", "shapenet"],
+                    help="inertia: the network shape (bob_spot: latent 2, 8 x 128; shapenet: latent 4, 8 x 256)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     r = np.random.default_rng(a.seed)
@@ -589,9 +591,11 @@ def main(argv=None):
         d0, d1 = np.abs(res["start"] - res["target"]).reshape(a.scenes, -1).max(1), np.abs(res["value"] - res["target"]).reshape(a.scenes, -1).max(1)
         print("%s: |x - x*| start mean %.4f -> final mean %.4f (max %.4f), %d scenes" % (a.goal, d0.mean(), d1.mean(), d1.max(), a.scenes))
     else:
+        # (the spin scene has no contacts, so it takes either network: the latent code acts through mesh and inertia only)
         from . import igr
-        packed = igr.pack_weights(*scenes.geometric_init_weights(a.seed, 0.5))
-        tgt, st = 0.1 * r.standard_normal((a.scenes, 2)), 0.1 * r.standard_normal((a.scenes, 2))
+        width, nlat = igr.SHAPES[a.net == "shapenet"]
+        packed = igr.pack_weights(*scenes.geometric_init_weights(a.seed, 0.5, width, nlat))
+        tgt, st = 0.1 * r.standard_normal((a.scenes, nlat)), 0.1 * r.standard_normal((a.scenes, nlat))
         dirs = r.standard_normal((a.scenes, 3)); dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
         fit_inertia_latent(tgt, st, dirs, packed, max_iter=a.iters, log=print)
 

@@ -101,7 +101,8 @@ def primitive_mesh(shape_type, prm_unit, res=128):
 class _IgrMeshSDF(torch.autograd.Function):
     """MeshSDF for the IGR network: forward = res^3 evaluations on the fp64 matrix cores + marching cubes; backward =
     dL/dlatent = sum_v -(dL/dv . n_v) d phi / d latent (v)  (bodies.py:680-702), normals and latent derivatives from
-    two more network evaluations at the vertices (dss_igr_query, dss_igr_query_latent_grad)."""
+    two more network evaluations at the vertices (igr_query: d phi / d xyz, and d phi / d latent with one column per
+    latent coordinate, 2 or 4)."""
 
     @staticmethod
     def forward(ctx, latent, packed_weights, res):
@@ -131,7 +132,7 @@ class _IgrMeshSDF(torch.autograd.Function):
         _, gl = igr_query(verts, lat, ctx.P, wrt="latent")      # d phi / d latent at the vertices
         nrm = gx / gx.norm(dim=1, keepdim=True).clamp_min(1e-12)
         dl_ds = -(grad_v * nrm).sum(1)
-        return (dl_ds[:, None] * gl[:, :2]).sum(0).to(ctx.ldev), None, None
+        return (dl_ds[:, None] * gl[:, :lat.numel()]).sum(0).reshape(lat.shape).to(ctx.ldev), None, None
 
 
 def igr_mesh(latent, packed_weights, res=128):

@@ -274,8 +274,11 @@ class SDF3D(Body3D):
         if net is None or grad_func is not None:
             raise NotImplementedError("SDF3D on the device path takes sdf_func=decode_igr(network) (a neural SDF the kernels "
                                       "can evaluate); arbitrary Python SDF functions cannot run inside the HIP stepper")
-        if len(params) != 1 or torch.as_tensor(params[0]).numel() != 2:
-            raise NotImplementedError("decode_igr networks with a 2-dimensional latent code (bob_spot_setup) are built")
+        from ..igr import packed_shape
+        self.latent_size = packed_shape(net.packed)[1]
+        if len(params) != 1 or torch.as_tensor(params[0]).numel() != self.latent_size:
+            raise NotImplementedError("SDF3D takes params=[latent] with the network's latent size (%d numbers for this one; "
+                                      "2 with the 128-wide and 4 with the 256-wide network are built)" % self.latent_size)
         self.igr = net
         self.sdf_func, self.params = sdf_func, params
         self.latent = get_tensor(params[0])
@@ -291,6 +294,10 @@ class SDF3D(Body3D):
     faces = property(lambda self: torch.as_tensor(self.faces_np))
 
     def shape_prm(self):
+        if self.latent_size > 2:
+            # the stepper carries three shape parameters per body, so a wider latent code never enters it: World3D steps such
+            # a body only where nothing can touch it, as a shape that is never queried (the sphere around its cube)
+            return torch.stack([self.scale.detach().reshape(()).to(torch.float64), *torch.zeros(2, dtype=torch.float64)])
         return torch.cat([self.latent.reshape(2).to(torch.float64), self.latent.new_zeros(1).to(torch.float64)])
 
     def shape_aux(self):

@@ -292,6 +292,15 @@ class World3D(BatchWorld3D):
         for i, b in enumerate(bodies):
             for o in b.no_contact:
                 nocon[i, idx[id(o)]] = 1
+        # A neural body whose latent code has more than the stepper's three shape parameters (the 256-wide network, latent 4)
+        # steps on the contact-free branch only: alone, or with every pair it belongs to in no_contact.  The kernels then never
+        # query its shape (a sphere stands in, as in experiments.spin_world); its mesh and inertia carry the latent gradient.
+        wide = [getattr(b, "igr", None) is not None and b.latent_size > 2 for b in bodies]
+        for i in range(nb):
+            if wide[i] and any(j != i and not (nocon[i, j] or nocon[j, i]) for j in range(nb)):
+                raise NotImplementedError("the stepper carries 3 shape parameters per body: a neural SDF body with a %d-number "
+                                          "latent code cannot take part in contacts (put every pair with it in no_contact)"
+                                          % bodies[i].latent_size)
         st = lambda f: torch.stack([f(b) for b in bodies])[None]
 
         def verts_param():       # pooled mesh vertices as a differentiable input, if any body's mesh depends on a parameter
@@ -309,7 +318,8 @@ class World3D(BatchWorld3D):
         npd = lambda x: x.detach().cpu().numpy()
         spec = dict(pose=npd(st(lambda b: b.p)), vel=npd(st(lambda b: b.v)), mass=npd(P["mass"]), inertia=npd(P["inertia"]),
                     restitution=npd(P["restitution"]), fric=npd(P["fric"]), fext=npd(P["fext"]),
-                    shape_type=np.array([[b.shape_type for b in bodies]], np.int32), shape_prm=npd(P["shape_prm"]),
+                    shape_type=np.array([[abi.SHAPE_SPHERE if w else b.shape_type for b, w in zip(bodies, wide)]], np.int32),
+                    shape_prm=npd(P["shape_prm"]),
                     shape_aux=np.array([[b.shape_aux() for b in bodies]], np.float64),
                     mesh_id=np.arange(nb, dtype=np.int32)[None], meshes=[(b.verts_np, b.faces_np) for b in bodies],
                     mesh_vgrad=[b.vgrad_np for b in bodies], Je=Je, no_contact=nocon)
@@ -322,7 +332,7 @@ class World3D(BatchWorld3D):
         nets = {id(b.igr): b.igr for b in bodies if getattr(b, "igr", None) is not None}
         if len(nets) > 1:
             raise NotImplementedError("all neural SDF bodies of a world share one network (one decode_igr(network))")
-        if nets:
+        if nets and not any(wide):
             spec["igr_net"] = next(iter(nets.values())).packed
         maxc = 32 * max(1, nb - 1)
         # level-set meshes (128^3 marching cubes, triangles of ~1/64 of the body's size) put thousands of faces within

@@ -169,16 +169,17 @@ def igr_pole(B, seed=0, packed=None, radius_init=0.5, latent_sigma=0.1, y0=6.0, 
     return spec
 
 
-def geometric_init_weights(seed=0, radius_init=0.5):
+def geometric_init_weights(seed=0, radius_init=0.5, width=128, latent=2):
     """IGR's geometric initialisation (Atzmon & Lipman 2020; the network constructor of the external IGR repository) for the
-    bob_spot_setup shape (IGR_data/train_configs/bob_spot_setup.conf:38-45): every hidden layer N(0, 2/out), the last layer
-    mean sqrt(pi)/sqrt(128) and bias -radius, seeded numpy.  Synthetic stand-in for the trained weights (README.md:41-42:
-    a download, unavailable offline)."""
+    bob_spot_setup shape (IGR_data/train_configs/bob_spot_setup.conf:38-45; width=256, latent=4: shapenet.conf): every hidden
+    layer N(0, 2/out), the last layer mean sqrt(pi)/sqrt(width) and bias -radius, seeded numpy.  Synthetic stand-in for the
+    trained weights (README.md:41-42: a download, unavailable offline)."""
     r = np.random.default_rng(seed)
-    dims = [5] + [128] * 8 + [1]
+    din = latent + 3
+    dims = [din] + [width] * 8 + [1]
     Ws, bs = [], []
     for l in range(9):
-        out = dims[l + 1] - 5 if l + 1 == 4 else dims[l + 1]
+        out = dims[l + 1] - din if l + 1 == 4 else dims[l + 1]
         if l == 8:
             Ws.append(r.normal(np.sqrt(np.pi) / np.sqrt(dims[l]), 1e-5, (out, dims[l]))); bs.append(np.full(out, -radius_init))
         else:

@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 
 # the header's #defines (DSS_<name>)
-ABI_VERSION = 2
+ABI_VERSION = 3
 CAND_FIELDS = 28
 CSCR_ROWS = 56
 N_ACTIVE_OVERFLOW = 1 << 30
@@ -56,11 +56,12 @@ def bind(L):
     return L
 
 
-IGR_NET_FIELDS = ("W0", "b0", "Wp", "bh", "W8", "b8")
+IGR_NET_POINTERS = ("W0", "b0", "Wp", "bh", "W8", "b8")
+IGR_NET_FIELDS = IGR_NET_POINTERS + ("width", "latent")      # hidden width and latent size: 0, 0 = the 128 / 2 network
 
 
 class DssIgrNet(ctypes.Structure):
-    _fields_ = [(k, _P) for k in IGR_NET_FIELDS]
+    _fields_ = [(k, _P if k in IGR_NET_POINTERS else _I) for k in IGR_NET_FIELDS]
 
 
 # (name, kind) kind: 'i' int scalar, 'd' double scalar, 'pd' double*, 'pi' int*, 'pb' uint8*
@@ -91,8 +92,9 @@ FIELDS = [
     ("tp_nu", "pd"), ("tp_abc", "pd"), ("tp_geom", "pd"),
     ("tp_nc", "pi"), ("tp_body", "pi"), ("tp_face", "pi"), ("tp_flags", "pi"), ("tp_t", "pd"),
     ("ev_lcp_start", "ev"), ("ev_lcp_stop", "ev"), ("ev_np_start", "ev"), ("ev_np_stop", "ev"),
-    # neural SDF bodies: DssIgrNet (six pointers), capacities, the round-based narrow phase's item state and query lists
-    *[("igr_" + k, "pd") for k in IGR_NET_FIELDS],
+    # neural SDF bodies: DssIgrNet (six pointers, width, latent size), capacities, the round-based narrow phase's item state and
+    # query lists
+    *[("igr_" + k, "pd" if k in IGR_NET_POINTERS else "i") for k in IGR_NET_FIELDS],
     ("igr_items_cap", "i"), ("igr_qcap", "i"), ("igr_rounds", "i"),
     ("igr_list", "pi"), ("igr_hdr", "pi"), ("igr_cface", "pi"), ("igr_cstate", "pi"), ("igr_cbuf", "pd"),
     ("igr_qpts", "pd"), ("igr_qlat", "pi"), ("igr_qtag", "pi"), ("igr_qsdf", "pd"), ("igr_qgrad", "pd"), ("igr_qn", "pi"),

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DSS_ABI_VERSION 2
+#define DSS_ABI_VERSION 3
 
 /* return codes of the launchers */
 #define DSS_OK 0
@@ -110,11 +110,16 @@ int dss_lcp_contact_backward(const double *Mblk, const double *A, const double *
  * the caller.  One "attempt" = solve -> integrate -> detect -> accept/halve for every active
  * scene (the reference's retry loop, world.py:249-356, run in lock step across the batch).
  * ------------------------------------------------------------------------------------ */
-/* The nine Linear layers of the IGR network (decode_igr, utils.py:330-350) in the layout the matrix-core kernel reads:
- * W0 [128][5], b0 [128]; Wp = the seven 128x128 layers in MFMA fragment order (dss_igr_packed_doubles() doubles,
- * diffsdfsim_amd/igr.py: pack_weights; layer 3's five missing rows are zero), bh [7][128]; W8 [128], b8 [1]. */
+/* The nine Linear layers of the IGR network (decode_igr, utils.py:330-350) in the layout the matrix-core kernel reads, for
+ * hidden width H and latent size L (input L + 3):
+ * W0 [H][L + 3], b0 [H]; Wp = the seven H x H layers in MFMA fragment order ([7][H/16][H/4][64] doubles,
+ * diffsdfsim_amd/igr.py: pack_weights; layer 3's L + 3 missing rows are zero), bh [7][H]; W8 [H], b8 [1].
+ * Built: (H, L) = (128, 2), bob_spot_setup.conf, and (256, 4), shapenet.conf; 0 in both fields means (128, 2).  The stepper
+ * (DssWorld.igr) runs the (128, 2) network only: shape_prm carries three numbers per body. */
 typedef struct DssIgrNet {
     const double *W0, *b0, *Wp, *bh, *W8, *b8;
+    int width;    /* H: 128 or 256 (0 = 128) */
+    int latent;   /* L: 2 or 4 (0 = 2) */
 } DssIgrNet;
 
 typedef struct DssWorld {
@@ -325,15 +330,18 @@ int dss_step_backward(const DssWorld *W, const DssAdjoint *A, void *stream);
  * body scale), latent [2]; W0 [128][5], b0 [128]; Wp = the seven 128x128 layers in MFMA fragment order
  * (dss_igr_packed_doubles() doubles, see diffsdfsim_amd/igr.py: pack_weights; layer 3's five missing rows are
  * zero), bh [7][128]; W8 [128], b8 [1].  Outputs sdf [n] and d sdf / d xyz [n][3] (not normalised).
+ * The network of IGR_data/train_configs/shapenet.conf (7 -> 256 x3 -> 249, skip, 256 x4 -> 1; latent [4]) goes through
+ * dss_igr_query_list with DssIgrNet.width = 256, .latent = 4 (operand shapes: see DssIgrNet).
  * ------------------------------------------------------------------------------------ */
-size_t dss_igr_packed_doubles(void);
+size_t dss_igr_packed_doubles(void);   /* doubles of Wp for the (128, 2) network: 7 * 8 * 32 * 64 */
 /* what a query round evaluates per point */
 #define DSS_IGR_XYZ 0      /* phi and d phi / d xyz (SDF3D.query_sdfs with return_grads, bodies.py:730-745) */
 #define DSS_IGR_LATENT 1   /* phi and d phi / d latent (MeshSDF backward, bodies.py:680-702; the stepper's latent adjoint) */
 #define DSS_IGR_VALUE 2    /* phi only (return_grads=False: candidate test, Laplacian probes, contacts.py:46-60, 184-196) */
 /* One evaluation round over a point list: pts [n][3] in the network's unit frame, point i uses the latent code
- * latents[lat_idx[i] * lat_stride + 0..1] (lat_idx NULL: code 0).  The list length is *n_dev if n_dev is non-NULL (device
- * memory, at most n_cap), else n_cap.  sdf [n]; grad [n][3] (unused for DSS_IGR_VALUE). */
+ * latents[lat_idx[i] * lat_stride + 0..L-1] (lat_idx NULL: code 0; lat_stride >= L).  The list length is *n_dev if n_dev is
+ * non-NULL (device memory, at most n_cap), else n_cap.  sdf [n]; grad [n][3] (unused for DSS_IGR_VALUE), except
+ * DSS_IGR_LATENT on a network with L = 4: grad [n][4], filled by two passes over the list. */
 int dss_igr_query_list(const DssIgrNet *net, const double *pts, const int *lat_idx, const double *latents, int lat_stride,
                        const int *n_dev, int n_cap, int mode, double *sdf, double *grad, void *stream);
 int dss_igr_query(const double *pts, const double *latent, const double *W0, const double *b0, const double *Wp,

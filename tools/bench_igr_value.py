@@ -3,11 +3,10 @@ import ctypes, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffsdfsim_amd import _lib, scenes
-from diffsdfsim_amd.igr import pack_weights
-from diffsdfsim_amd.world_abi import IGR_NET_FIELDS, DssIgrNet
-P = pack_weights(*scenes.geometric_init_weights(0, 0.5))
+from diffsdfsim_amd import igr
+P = igr.pack_weights(*scenes.geometric_init_weights(0, 0.5))
 L = _lib.lib()
-net = DssIgrNet(*[P[k].data_ptr() for k in IGR_NET_FIELDS])
+net = igr.net_struct(P)
 for n in (240_000, 60_000, 1_000_000):
     pts = torch.rand(n, 3, dtype=torch.float64, device="cuda") * 1.6 - 0.8
     lat = torch.zeros(1, 3, dtype=torch.float64, device="cuda")
