@@ -305,6 +305,8 @@ inline namespace shapes_lean {
 #endif
 enum ShapeType { SHAPE_BOX = 0, SHAPE_SPHERE = 1, SHAPE_CYLINDER = 2, SHAPE_BOX_ROUNDED = 3, SHAPE_BRICK = 4, SHAPE_BOWL = 5, SHAPE_IGR = 6, SHAPE_GRID = 7 };
 
+constexpr int IGR_LAT_MAX = 4;   // DSS_IGR_LATENT_MAX: the widest latent code a neural body carries
+
 template <class T> struct Shape {
     int type;
     T prm[3];   // box / rounded box / brick: dims ; sphere: rad ; cylinder: rad, height (axis = body z) ; bowl: r, d
@@ -315,6 +317,8 @@ template <class T> struct Shape {
     // neural SDF (SHAPE_IGR) in the reverse sweep: records of the network's value and derivatives at the points this body is
     // queried at for ONE contact (igr_lin below), evaluated beforehand on the matrix cores; NULL elsewhere
     const double *lin;
+    T lat[IGR_LAT_MAX];   // the body's latent code as igr_lin differentiates it (first nlat entries; set_latent)
+    int nlat;
     // voxel-grid SDF (SHAPE_GRID, SDFGrid3D bodies.py:203-257, 763-775): samples over the unit cube, x slowest
     const double *grid;
     int gn[3];
@@ -328,6 +332,7 @@ template <class T> __host__ __device__ inline void make_shape(Shape<T> &s, int t
 #if DSS_ALL_SHAPES
     s.hr = T(0.0);
     s.lin = nullptr;
+    s.nlat = 0;
     s.grid = nullptr;
     s.gn[0] = s.gn[1] = s.gn[2] = 0;
 #endif
@@ -372,6 +377,7 @@ template <class T> __host__ __device__ inline void make_unit_shape(Shape<T> &s, 
     s.scale = T(1.0);
     s.hr = au;
     s.lin = nullptr;
+    s.nlat = 0;
     s.grid = nullptr;
     s.gn[0] = s.gn[1] = s.gn[2] = 0;
     if (type == SHAPE_BOX) for (int i = 0; i < 3; ++i) s.hd[i] = pu[i] / 2.0;          // box_sdf: half_dims = dims / 2
@@ -554,16 +560,25 @@ template <class T> __host__ __device__ inline void sdf_unit(const Shape<T> &s, c
 // A neural SDF body's query as the reference's autograd sees it (SDF3D.query_sdfs, bodies.py:727-745: the input gradient is
 // taken WITHOUT create_graph, so the normal is a constant; the value keeps the graph to the point and to the latent code):
 //   phi(pt, latent) = phi0 + raw . (pt - pt0) + dlat . (latent - latent0),   g = nrm   (constant)
-// record `rec` of s.lin: phi0, raw[3] = d phi / d pt, dlat[2] = d phi / d latent (both in world units), nrm[3].
-constexpr int IGR_LIN = 9;
+// record `rec` of s.lin: phi0, raw[3] = d phi / d pt, dlat[IGR_LAT_MAX] = d phi / d latent (both in world units; entries beyond
+// the network's latent size are zero), nrm[3].
+constexpr int IGR_LIN_NRM = 4 + IGR_LAT_MAX, IGR_LIN = IGR_LIN_NRM + 3;
+// the latent code of a neural body: `code` = its nlat numbers (seeded by the caller where their adjoint is wanted)
+template <class T> __host__ __device__ inline void set_latent(Shape<T> &s, const T *code, int nlat)
+{
+    s.nlat = nlat;
+    for (int j = 0; j < IGR_LAT_MAX; ++j) if (j < nlat) s.lat[j] = code[j];
+}
 template <class T> __host__ __device__ inline void igr_lin(const Shape<T> &s, int rec, const T *pt, T &phi, T *g)
 {
     const double *r = s.lin + IGR_LIN * rec;
     T acc = T(r[0]);
     for (int i = 0; i < 3; ++i) acc = acc + (pt[i] - val(pt[i])) * r[1 + i];
-    for (int j = 0; j < 2; ++j) acc = acc + (s.prm[j] - val(s.prm[j])) * r[4 + j];
+    // (over the code's own length: the two-number code of the 128-wide network sums the two terms it always did)
+#pragma unroll
+    for (int j = 0; j < IGR_LAT_MAX; ++j) if (j < s.nlat) acc = acc + (s.lat[j] - val(s.lat[j])) * r[4 + j];
     phi = acc;
-    for (int i = 0; i < 3; ++i) g[i] = T(r[6 + i]);
+    for (int i = 0; i < 3; ++i) g[i] = T(r[IGR_LIN_NRM + i]);
 }
 #endif
 

@@ -258,14 +258,14 @@ igr_query_kernel(Query Q, const double *W0, const double *b0, const double *Wp, 
 // rest the gradient list.  Both lists are short most of the time (a Frank-Wolfe round: a few points per item), so each on
 // its own is a launch whose duration is the latency of one tile through nine layers, with most of the chip idle -- and
 // there are 42 rounds per detection.
-template <int NW, int NG> __global__ void __launch_bounds__(64 * NW)
+template <class NET, int NW, int NG> __global__ void __launch_bounds__(64 * NW, NET::WAVES_PER_SIMD)
 igr_query2_kernel(Query Qv, Query Qg, int split, const double *W0, const double *b0, const double *Wp, const double *bh,
                   const double *W8, const double *b8)
 {
     DSS_DYN_LDS(double, X);
     const int bid = (int)blockIdx.x;
-    if (bid < split) igr_body<NetBobSpot, NW, NG, MODE_VALUE>(Qv, bid, split, X, W0, b0, Wp, bh, W8, b8);
-    else igr_body<NetBobSpot, NW, NG, MODE_XYZ>(Qg, bid - split, (int)gridDim.x - split, X, W0, b0, Wp, bh, W8, b8);
+    if (bid < split) igr_body<NET, NW, NG, MODE_VALUE>(Qv, bid, split, X, W0, b0, Wp, bh, W8, b8);
+    else igr_body<NET, NW, NG, MODE_XYZ>(Qg, bid - split, (int)gridDim.x - split, X, W0, b0, Wp, bh, W8, b8);
 }
 
 template <class NET, int NW, int NG, int MODE>
@@ -303,13 +303,13 @@ template <int PTS> inline long tiles_for(int n_cap, int est)
     if (tiles > 256L * 2 * 4) tiles = 256L * 2 * 4;
     return tiles < 1 ? 1 : tiles;
 }
-template <int NW, int NG> void launch2(const Query &Qv, const Query &Qg, const DssIgrNet &N, int n_cap, int estv, int estg, hipStream_t stream)
+template <class NET, int NW, int NG> void launch2(const Query &Qv, const Query &Qg, const DssIgrNet &N, int n_cap, int estv, int estg, hipStream_t stream)
 {
-    const size_t lds = (size_t)16 * NG * NetBobSpot::LDX * sizeof(double);
+    const size_t lds = (size_t)16 * NG * NET::LDX * sizeof(double);
     if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute((const void *)igr_query2_kernel<NW, NG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void *)igr_query2_kernel<NET, NW, NG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const long tv = tiles_for<16 * NG>(n_cap, estv), tg = tiles_for<4 * NG>(n_cap, estg);
-    hipLaunchKernelGGL((igr_query2_kernel<NW, NG>), dim3((unsigned)(tv + tg)), dim3(64 * NW), lds, stream, Qv, Qg, (int)tv, N.W0, N.b0,
+    hipLaunchKernelGGL((igr_query2_kernel<NET, NW, NG>), dim3((unsigned)(tv + tg)), dim3(64 * NW), lds, stream, Qv, Qg, (int)tv, N.W0, N.b0,
                        N.Wp, N.bh, N.W8, N.b8);
 }
 
@@ -380,14 +380,19 @@ int launch_igr_pair(const DssIgrNet &N, const double *pts_v, const int *lat_v, c
                     const int *lat_g, const int *n_g, double *sdf_g, double *grad_g, const double *latents, int lat_stride, int n_cap,
                     hipStream_t stream, int est_v, int est_g)
 {
-    // (the stepper carries three shape parameters per body: its query rounds exist for the 128 / 2 network only)
-    if (net_kind(N) != NET_BOB_SPOT) return DSS_E_UNSUPPORTED;
+    const int kind = net_kind(N);
+    if (kind < 0) return DSS_E_UNSUPPORTED;
     Query Qv{pts_v, lat_v, latents, lat_stride, 0, n_v, n_cap, sdf_v, nullptr}, Qg{pts_g, lat_g, latents, lat_stride, 0, n_g, n_cap, sdf_g, grad_g};
     // variant by the work expected (a gradient point is four rows): see launch_mode
     const long rows = (est_v < 0 || est_g < 0) ? (long)n_cap : (long)est_v + 4L * est_g;
-    if (rows >= 16 * 1024) launch2<4, 2>(Qv, Qg, N, n_cap, est_v, est_g, stream);
-    else if (rows >= 2 * 1024) launch2<2, 2>(Qv, Qg, N, n_cap, est_v, est_g, stream);
-    else launch2<4, 1>(Qv, Qg, N, n_cap, est_v, est_g, stream);
+    if (kind == NET_SHAPENET) {
+        // the workgroup shapes of Variants<NetShapenet>: 8 waves, one row group for the short rounds, two from 2048 rows
+        if (rows >= 2 * 1024) launch2<NetShapenet, 8, 2>(Qv, Qg, N, n_cap, est_v, est_g, stream);
+        else launch2<NetShapenet, 8, 1>(Qv, Qg, N, n_cap, est_v, est_g, stream);
+    }
+    else if (rows >= 16 * 1024) launch2<NetBobSpot, 4, 2>(Qv, Qg, N, n_cap, est_v, est_g, stream);
+    else if (rows >= 2 * 1024) launch2<NetBobSpot, 2, 2>(Qv, Qg, N, n_cap, est_v, est_g, stream);
+    else launch2<NetBobSpot, 4, 1>(Qv, Qg, N, n_cap, est_v, est_g, stream);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }
 }  // namespace dss

@@ -625,7 +625,8 @@ int launch_igr_rounds(const DssWorld &W, hipStream_t stream)
             if (W.igr_ev) (void)hipEventRecord((hipEvent_t)W.igr_ev[4 * r], stream);
             const int rc = launch_igr_pair(W.igr, W.igr_qpts + ov * 3, W.igr_qlat + ov, W.igr_qn + 2 * r + L_VALUE, W.igr_qsdf + ov,
                                            W.igr_qpts + og * 3, W.igr_qlat + og, W.igr_qn + 2 * r + L_GRAD, W.igr_qsdf + og,
-                                           W.igr_qgrad + (size_t)set * W.igr_qcap * 3, W.shape_prm, 3, W.igr_qcap, stream,
+                                           W.igr_qgrad + (size_t)set * W.igr_qcap * 3, W.igr_latent ? W.igr_latent : W.shape_prm,
+                                           W.igr_latent ? DSS_IGR_LATENT_MAX : 3, W.igr_qcap, stream,
                                            W.igr_hint ? W.igr_hint[2 * r + L_VALUE] : -1, W.igr_hint ? W.igr_hint[2 * r + L_GRAD] : -1);
             if (W.igr_ev) (void)hipEventRecord((hipEvent_t)W.igr_ev[4 * r + 1], stream);
             if (rc) return rc;

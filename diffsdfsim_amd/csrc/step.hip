@@ -231,6 +231,8 @@ inline int check_world(const DssWorld *W)
     if (W->B <= 0 || W->nb <= 0 || W->nb > 64 || W->maxc <= 0) return DSS_E_BADARG;
     if (W->fric_dirs != 4 && W->fric_dirs != 8) return DSS_E_BADARG;
     if (6 * W->nb + W->neq > 64) return DSS_E_UNSUPPORTED;
+    // a latent code of more than three numbers does not fit a shape_prm row: it comes from the latent table
+    if (W->igr.W0 && W->igr.latent > 3 && !W->igr_latent) return DSS_E_BADARG;
     return DSS_OK;
 }
 

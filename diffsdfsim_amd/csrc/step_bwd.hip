@@ -89,6 +89,8 @@ __device__ inline void bwd_select(const DssWorld &W, const DssAdjoint &A, int sc
 }
 
 // d(n, p1, p2)/d(pose1, pose2, prm1, prm2) contracted with gbar[9]; out[20] = q1(4) x1(3) q2(4) x2(3) prm1(3) prm2(3).
+// Full variant: out[CONTACT_VJP_OUT], where prm1 / prm2 of a neural body with a row in the latent table (DssWorld.igr_latent)
+// are the first three derivatives w.r.t. its latent code and out[20] / out[21] the fourth (body 1 / body 2); 22-27 scratch.
 // Forward-mode duals, four seeds per pass.  Only q1 and prm1 enter the body-1 half of the contact (contact_head: two
 // SDF queries and the Newton step): they take two full passes.  q2, x2 and prm2 enter the body-2 half alone
 // (contact_tail: one query, two rotations), so their three passes differentiate that half with the head as constants;
@@ -101,12 +103,27 @@ template <class T> __device__ inline void attach_grid(const DssWorld &W, int sc,
     s.grid = W.grid_data + W.grid_off[gi];
     for (int i = 0; i < 3; ++i) s.gn[i] = W.grid_dims[3 * gi + i];
 }
+// the latent code of a neural body: its row of the latent table (constants here; contact_vjp seeds them in the pass that
+// differentiates them), or without a table shape parameters 0 and 1 with whatever seeds the caller gave those
+inline __device__ const double *latent_row(const DssWorld &W, int sc, int b)
+{
+    return (W.igr_latent && W.shape_type[(size_t)sc * W.nb + b] == DSS_SHAPE_IGR) ? W.igr_latent + ((size_t)sc * W.nb + b) * DSS_IGR_LATENT_MAX : nullptr;
+}
+template <class T> __device__ inline void attach_latent(const DssWorld &W, const double *row, Shape<T> &s, const T *prm)
+{
+    static_assert(IGR_LAT_MAX == DSS_IGR_LATENT_MAX, "geom.h and the ABI agree on the widest latent code");
+    if (s.type != SHAPE_IGR) return;
+    T code[IGR_LAT_MAX];
+    for (int j = 0; j < IGR_LAT_MAX; ++j) code[j] = row ? T(row[j]) : prm[j < 2 ? j : 0];
+    set_latent(s, code, row ? (W.igr.latent ? W.igr.latent : 2) : 2);
+}
 #endif
 // lin1 / lin2: igr_lin records of a neural body 1 / body 2 for this contact (NULL: analytic body); stable_in >= 0: which
 // body's normal the contact used, decided by the caller (for neural bodies the Laplacian probes are not repeated).
 // Forward mode (five dual-number passes): the full variant (every primitive, neural / grid bodies, mesh-vertex adjoints).  The
 // lean variant -- box / sphere / cylinder, what the benchmark configs run -- uses the reverse-mode adjoint of contact_rev.h.
 #if DSS_ALL_SHAPES
+constexpr int CONTACT_VJP_OUT = 28;
 __device__ void contact_vjp(const DssWorld &W, int sc, const double *pose_n, int b1, int b2, int face,
                             const double *abc, const double *gbar, double *out, double *g_verts,
                             const double *lin1 = nullptr, const double *lin2 = nullptr, int stable_in = -1)
@@ -129,6 +146,9 @@ __device__ void contact_vjp(const DssWorld &W, int sc, const double *pose_n, int
     double tv[3][3], tg[3][3];
     for (int v = 0; v < 3; ++v)
         for (int i = 0; i < 3; ++i) { tv[v][i] = W.verts[(size_t)(voff + fv[v]) * 3 + i]; tg[v][i] = W.vgrad[(size_t)(voff + fv[v]) * 3 + i]; }
+    // a neural body whose code lives in the latent table: the parameter pass of that body seeds the code's (up to four)
+    // numbers in place of the three shape parameters, which such a body does not read
+    const double *lt1 = latent_row(W, sc, b1), *lt2 = latent_row(W, sc, b2);
     // value pass: the head as constants for the body-2 passes, and the normal-selection decision for all of them
     int stable = stable_in;
     double cp1v[3], n1v[3], d1v, p1v[3];
@@ -140,18 +160,24 @@ __device__ void contact_vjp(const DssWorld &W, int sc, const double *pose_n, int
         make_shape(B2.shape, ty2, prm2, aux2);
 #if DSS_ALL_SHAPES
         B1.shape.lin = lin1; B2.shape.lin = lin2; attach_grid(W, sc, b1, B1.shape); attach_grid(W, sc, b2, B2.shape);
+        attach_latent(W, lt1, B1.shape, prm1); attach_latent(W, lt2, B2.shape, prm2);
 #endif
         double nn[3], pp2[3], pen;
         contact_head(B1, tv, abc, cp1v, n1v, d1v, p1v);
         contact_tail(B1, B2, cp1v, n1v, d1v, p1v, 1e-3, nn, pp2, pen, &stable);
     }
-    for (int t = 0; t < 20; ++t) out[t] = 0.0;
+    for (int t = 0; t < CONTACT_VJP_OUT; ++t) out[t] = 0.0;
     auto contract = [&](const D *n, const D *p1, const D *p2, int slot0, int cnt) {
         for (int s = 0; s < cnt; ++s) {
             double acc = 0.0;
             for (int i = 0; i < 3; ++i) acc += gbar[i] * n[i].d[s] + (p1 ? gbar[3 + i] * p1[i].d[s] : 0.0) + gbar[6 + i] * p2[i].d[s];
             out[slot0 + s] = acc;
         }
+    };
+    // seeds of a table-held latent code: coordinate j on dual slot j
+    auto seed_latent = [](Shape<D> &s) {
+#pragma unroll
+        for (int j = 0; j < IGR_LAT_MAX; ++j) if (j < s.nlat) s.lat[j].d[j] = 1.0;
     };
     // ---- body-1 inputs: full passes, seeds q1 | prm1 -------------------------------------------------------
 #pragma unroll
@@ -161,19 +187,21 @@ __device__ void contact_vjp(const DssWorld &W, int sc, const double *pose_n, int
         for (int i = 0; i < 4; ++i) { B1.q[i] = D(P1[i]); if (grp == 0) B1.q[i].d[i] = 1.0; B2.q[i] = D(P2[i]); }
         for (int i = 0; i < 3; ++i) {
             B1.pos[i] = D(P1[4 + i]); B2.pos[i] = D(P2[4 + i]);
-            pr1[i] = D(prm1[i]); if (grp == 1) pr1[i].d[i] = 1.0;
+            pr1[i] = D(prm1[i]); if (grp == 1 && !lt1) pr1[i].d[i] = 1.0;
             pr2[i] = D(prm2[i]);
         }
         make_shape(B1.shape, ty1, pr1, aux1);
         make_shape(B2.shape, ty2, pr2, aux2);
 #if DSS_ALL_SHAPES
         B1.shape.lin = lin1; B2.shape.lin = lin2; attach_grid(W, sc, b1, B1.shape); attach_grid(W, sc, b2, B2.shape);
+        attach_latent(W, lt1, B1.shape, pr1); attach_latent(W, lt2, B2.shape, pr2);
+        if (grp == 1 && lt1) seed_latent(B1.shape);
 #endif
         D tri[3][3];
         for (int v = 0; v < 3; ++v)
             for (int i = 0; i < 3; ++i) {
                 D d(tv[v][i]);
-                if (grp == 1) {
+                if (grp == 1 && !lt1) {
                     // box: own axis; sphere: radius; cylinder: x,y <- rad, z <- height
                     const int s = (ty1 == SHAPE_BOX || ty1 == SHAPE_BOX_ROUNDED || ty1 == SHAPE_BRICK) ? i : ((ty1 == SHAPE_CYLINDER && i == 2) ? 1 : 0);
 #pragma unroll
@@ -184,7 +212,10 @@ __device__ void contact_vjp(const DssWorld &W, int sc, const double *pose_n, int
         D n[3], p1[3], p2[3], pen;
         contact_from_bary(B1, B2, tri, abc, 1e-3, n, p1, p2, pen, &stable, det2);
         if (grp == 0) contract(n, p1, p2, 0, 4);
-        else contract(n, p1, p2, 14, 3);
+        else {
+            if (lt1) contract(n, p1, p2, 20, 4);      // slots 20-22 are copied to 14-16 below: contract(.., 14, 4) would run into body 2's
+            else contract(n, p1, p2, 14, 3);
+        }
     }
     // ---- body-2 inputs: the tail alone, seeds q2 | x2 | prm2 -----------------------------------------------
 #pragma unroll
@@ -196,20 +227,28 @@ __device__ void contact_vjp(const DssWorld &W, int sc, const double *pose_n, int
             B1.pos[i] = D(P1[4 + i]);
             B2.pos[i] = D(P2[4 + i]); if (grp == 1) B2.pos[i].d[i] = 1.0;
             pr1[i] = D(prm1[i]);
-            pr2[i] = D(prm2[i]); if (grp == 2) pr2[i].d[i] = 1.0;
+            pr2[i] = D(prm2[i]); if (grp == 2 && !lt2) pr2[i].d[i] = 1.0;
         }
         make_shape(B1.shape, ty1, pr1, aux1);
         make_shape(B2.shape, ty2, pr2, aux2);
 #if DSS_ALL_SHAPES
         B1.shape.lin = lin1; B2.shape.lin = lin2; attach_grid(W, sc, b1, B1.shape); attach_grid(W, sc, b2, B2.shape);
+        attach_latent(W, lt1, B1.shape, pr1); attach_latent(W, lt2, B2.shape, pr2);
+        if (grp == 2 && lt2) seed_latent(B2.shape);
 #endif
         D cp1[3], n1[3], d1(d1v), p1[3], n[3], p2[3], pen;
         for (int i = 0; i < 3; ++i) { cp1[i] = D(cp1v[i]); n1[i] = D(n1v[i]); p1[i] = D(p1v[i]); }
         contact_tail(B1, B2, cp1, n1, d1, p1, 1e-3, n, p2, pen, &stable, det2);
         if (grp == 0) contract(n, nullptr, p2, 7, 4);
         else if (grp == 1) { contract(n, nullptr, p2, 11, 3); for (int i = 0; i < 3; ++i) out[4 + i] = -out[11 + i]; }
+        else if (lt2) contract(n, nullptr, p2, 24, 4);
         else contract(n, nullptr, p2, 17, 3);
     }
+    // a table-held code: its first three derivatives take the parameter slots (14-16 / 17-19), the fourth slot 20 / 21
+    if (lt1) { for (int i = 0; i < 3; ++i) out[14 + i] = out[20 + i]; out[20] = out[23]; }
+    else out[20] = 0.0;
+    if (lt2) { for (int i = 0; i < 3; ++i) out[17 + i] = out[24 + i]; out[21] = out[27]; }
+    else out[21] = 0.0;
 #if DSS_ALL_SHAPES
     // ---- the triangle's vertices (full variant): one full pass per vertex, seeds = its three coordinates -----------
     // Level-set meshes have no per-vertex parameter tangent (vgrad = 0); their shape gradient flows through the vertex
@@ -224,6 +263,7 @@ __device__ void contact_vjp(const DssWorld &W, int sc, const double *pose_n, int
             make_shape(B2.shape, ty2, pr2, aux2);
 #if DSS_ALL_SHAPES
             B1.shape.lin = lin1; B2.shape.lin = lin2; attach_grid(W, sc, b1, B1.shape); attach_grid(W, sc, b2, B2.shape);
+            attach_latent(W, lt1, B1.shape, pr1); attach_latent(W, lt2, B2.shape, pr2);
 #endif
             D tri[3][3];
             for (int v = 0; v < 3; ++v)
@@ -307,6 +347,8 @@ __device__ void igr_records(const DssWorld &W, const DssAdjoint &A, int sc, cons
     const int nb = W.nb, MX = W.maxc, b1 = v.body_n[c], b2 = v.body_n[MX + c];
     const size_t cap = (size_t)W.B * 2 * MX;
     const double *sdfX = A.igr_bw_sdf, *gX = A.igr_bw_grad, *gL = A.igr_bw_grad + cap * 3;
+    // the latent pass writes rows of three (two derivatives and a zero), or of four for a four-number code (igr_mlp.hip)
+    const int nl = W.igr.latent ? W.igr.latent : 2, ls = nl > 3 ? nl : 3;
     const double *P1 = v.pose_n + 7 * b1;
     for (int i = 0; i < 3 * IGR_LIN; ++i) lin[i] = 0.0;
     auto fill = [&](double *r, int idx, double scale) {
@@ -314,8 +356,8 @@ __device__ void igr_records(const DssWorld &W, const DssAdjoint &A, int sc, cons
         r[0] = sdfX[idx] * scale;
         const double raw[3] = {gX[(size_t)idx * 3], gX[(size_t)idx * 3 + 1], gX[(size_t)idx * 3 + 2]};
         for (int i = 0; i < 3; ++i) r[1 + i] = raw[i];                  // d (scale f(pt / scale)) / d pt
-        for (int j = 0; j < 2; ++j) r[4 + j] = gL[(size_t)idx * 3 + j] * scale;
-        normalize(raw, r + 6);
+        for (int j = 0; j < nl; ++j) r[4 + j] = gL[(size_t)idx * ls + j] * scale;
+        normalize(raw, r + IGR_LIN_NRM);
     };
     if (i1 != -1) fill(lin, i1, W.shape_aux[(size_t)sc * nb + b1]);
     if (i2 != -1) fill(lin + 2 * IGR_LIN, i2, W.shape_aux[(size_t)sc * nb + b2]);
@@ -325,7 +367,7 @@ __device__ void igr_records(const DssWorld &W, const DssAdjoint &A, int sc, cons
     if (i1 != -1 && !stable) {       // the normal used is body 1's after the Newton step: n = -R1 n1'  ->  n1' = -R1^T n
         double t[3];
         quat_apply_inv(P1, nt, t);
-        for (int i = 0; i < 3; ++i) lin[IGR_LIN + 6 + i] = -t[i];
+        for (int i = 0; i < 3; ++i) lin[IGR_LIN + IGR_LIN_NRM + i] = -t[i];
     }
 }
 #endif
@@ -508,11 +550,18 @@ __global__ void __launch_bounds__(64) bwd_pre_kernel(DssWorld W_arg, DssAdjoint 
 
     // (a) contacts detected after the sub-step: geometry adjoint -> pose after the sub-step, shape params
     for (int c = lane; c < v.nc_n; c += 64) {
+#if DSS_ALL_SHAPES
+        double gb[9], out[CONTACT_VJP_OUT];
+#else
         double gb[9], out[20];
+#endif
         for (int i = 0; i < 9; ++i) gb[i] = a_geom[(size_t)i * MX + c];
         const double abc[3] = {v.abc_n[c], v.abc_n[MX + c], v.abc_n[2 * MX + c]};
         if (v.face_n[c] < 0) {      // a contact kept from a penetrating direction (world.py:345-347): computed under no_grad
             for (int i = 0; i < 20; ++i) cs[(size_t)i * MX + c] = 0.0;
+#if DSS_ALL_SHAPES
+            cs[(size_t)54 * MX + c] = 0.0; cs[(size_t)55 * MX + c] = 0.0;
+#endif
             continue;
         }
         const double *l1 = nullptr, *l2 = nullptr;
@@ -547,17 +596,32 @@ __global__ void __launch_bounds__(64) bwd_pre_kernel(DssWorld W_arg, DssAdjoint 
         }
 #endif
         for (int i = 0; i < 20; ++i) cs[(size_t)i * MX + c] = out[i];
+#if DSS_ALL_SHAPES
+        cs[(size_t)54 * MX + c] = out[20]; cs[(size_t)55 * MX + c] = out[21];   // fourth latent derivative of body 1 / body 2
+#endif
     }
     __syncthreads();
-    __shared__ double s_sums[64 * 10];
-    {
-        static constexpr int row0[10] = {0, 1, 2, 3, 4, 5, 6, 14, 15, 16}, row1[10] = {7, 8, 9, 10, 11, 12, 13, 17, 18, 19};
-        contact_sums<10>(v.body_n, MX, v.nc_n, nb, cs, row0, row1, s_sums);
-    }
+    // per body: pose (7), shape parameters (3) and, full variant, the fourth number of a table-held latent code
+#if DSS_ALL_SHAPES
+    constexpr int NS = 11;
+    static constexpr int row0[NS] = {0, 1, 2, 3, 4, 5, 6, 14, 15, 16, 54}, row1[NS] = {7, 8, 9, 10, 11, 12, 13, 17, 18, 19, 55};
+#else
+    constexpr int NS = 10;
+    static constexpr int row0[NS] = {0, 1, 2, 3, 4, 5, 6, 14, 15, 16}, row1[NS] = {7, 8, 9, 10, 11, 12, 13, 17, 18, 19};
+#endif
+    __shared__ double s_sums[64 * NS];
+    contact_sums<NS>(v.body_n, MX, v.nc_n, nb, cs, row0, row1, s_sums);
     if (lane < nb) {
         double ap[7], gp[3];
-        for (int i = 0; i < 7; ++i) ap[i] = a_pose[7 * lane + i] + s_sums[10 * lane + i];
-        for (int i = 0; i < 3; ++i) gp[i] = s_sums[10 * lane + 7 + i];
+        for (int i = 0; i < 7; ++i) ap[i] = a_pose[7 * lane + i] + s_sums[NS * lane + i];
+        for (int i = 0; i < 3; ++i) gp[i] = s_sums[NS * lane + 7 + i];
+#if DSS_ALL_SHAPES
+        if (latent_row(W, sc, lane)) {      // (the parameter slots of such a body hold latent derivatives: g_prm stays as it is)
+            double *gl = A.g_latent + ((size_t)sc * nb + lane) * DSS_IGR_LATENT_MAX;
+            for (int i = 0; i < 3; ++i) gl[i] += gp[i];
+            gl[3] += s_sums[NS * lane + 10];
+        } else
+#endif
         for (int i = 0; i < 3; ++i) A.g_prm[((size_t)sc * nb + lane) * 3 + i] += gp[i];
         if (ev) {   // pieces of H.backward that land on this body: moved pose, new velocity, f/m
             double vx[6] = {0, 0, 0, 0, 0, 0}, ab[3] = {0, 0, 0};
@@ -770,8 +834,10 @@ void launch_bwd_pre_all(const DssWorld &W, const DssAdjoint &A, hipStream_t stre
         const int cap = W.B * 2 * W.maxc;
         (void)hipMemsetAsync(A.igr_bw_n, 0, sizeof(int), stream);
         hipLaunchKernelGGL(bwd_igr_prep_kernel, dim3(W.B), dim3(64), 0, stream, W, A);
-        launch_igr_list(W.igr, A.igr_bw_pts, A.igr_bw_lat, W.shape_prm, 3, A.igr_bw_n, cap, DSS_IGR_XYZ, A.igr_bw_sdf, A.igr_bw_grad, stream, W.B * 8);
-        launch_igr_list(W.igr, A.igr_bw_pts, A.igr_bw_lat, W.shape_prm, 3, A.igr_bw_n, cap, DSS_IGR_LATENT, A.igr_bw_sdf + cap,
+        const double *lat = W.igr_latent ? W.igr_latent : W.shape_prm;
+        const int stride = W.igr_latent ? DSS_IGR_LATENT_MAX : 3;
+        launch_igr_list(W.igr, A.igr_bw_pts, A.igr_bw_lat, lat, stride, A.igr_bw_n, cap, DSS_IGR_XYZ, A.igr_bw_sdf, A.igr_bw_grad, stream, W.B * 8);
+        launch_igr_list(W.igr, A.igr_bw_pts, A.igr_bw_lat, lat, stride, A.igr_bw_n, cap, DSS_IGR_LATENT, A.igr_bw_sdf + cap,
                         A.igr_bw_grad + (size_t)cap * 3, stream, W.B * 8);
     }
     hipLaunchKernelGGL(bwd_pre_kernel, dim3(W.B), dim3(64), 0, stream, W, A);
@@ -785,6 +851,8 @@ size_t dss_adjoint_sizeof(void) { return sizeof(DssAdjoint); }
 int dss_step_backward(const DssWorld *W, const DssAdjoint *A, void *stream_)
 {
     if (!W || !A || !W->tp_pose) return DSS_E_BADARG;
+    // a latent code of more than three numbers comes from the latent table, and a table's adjoint needs somewhere to go
+    if ((W->igr.W0 && W->igr.latent > 3 && !W->igr_latent) || (W->igr_latent && !A->g_latent)) return DSS_E_BADARG;
     hipStream_t stream = (hipStream_t)stream_;
     if (W->shape_rare) dss::launch_bwd_pre_all(*W, *A, stream);
     else hipLaunchKernelGGL(bwd_pre_kernel, dim3(W->B), dim3(64), 0, stream, *W, *A);

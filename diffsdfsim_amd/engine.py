@@ -105,12 +105,39 @@ def mesh_table(meshes, vgrads=None):
     return out
 
 
+def check_igr_spec(spec):
+    """What a spec with neural SDF bodies must say about their latent codes (no device needed).  Returns the latent table
+    [B, nb, IGR_LATENT_MAX] as float64, or None when the codes are shape_prm[..., :2] (the 5 -> 8 x 128 -> 1 network).
+    The 7 -> 8 x 256 -> 1 network's four-number code does not fit a shape_prm row: it needs spec['igr_latent']."""
+    from . import igr
+    B, nb = np.asarray(spec["pose"]).shape[:2]
+    if spec.get("igr_net") is None:
+        raise ValueError("a body of shape_type SHAPE_IGR needs spec['igr_net'] (diffsdfsim_amd.igr.pack_weights)")
+    shape = igr.packed_shape(spec["igr_net"])
+    if shape not in igr.SHAPES:
+        raise NotImplementedError("no kernels are built for a network of width %d and latent size %d" % tuple(shape))
+    lat = spec.get("igr_latent")
+    if shape == igr.SHAPES[0]:
+        if lat is not None:
+            raise ValueError("spec['igr_latent'] goes with the 7 -> 8 x 256 -> 1 network; the 5 -> 8 x 128 -> 1 network's "
+                             "2-number latent code is shape_prm[..., :2]")
+        return None
+    if lat is None:
+        raise ValueError("the 7 -> 8 x 256 -> 1 network's 4-number latent code does not fit the 3 shape parameters per body: "
+                         "give spec['igr_latent'] [B, nb, %d]" % abi.IGR_LATENT_MAX)
+    lat = np.asarray(lat, np.float64)
+    if lat.shape != (B, nb, abi.IGR_LATENT_MAX):
+        raise ValueError("spec['igr_latent'] has shape %s, expected %s" % (lat.shape, (B, nb, abi.IGR_LATENT_MAX)))
+    return lat
+
+
 class BatchEngine:
     def __init__(self, spec, dt=1.0 / 30, eps=1e-3, tol=1e-8, fric_dirs=8, maxc=64, max_cand=1024, max_pc=32,
                  max_sub=0, strict_no_pen=True, toc_diff=True, lcp_max_iter=10, backend=None, grad_flags=0):
         """``spec``: numpy arrays pose [B,nb,7], vel [B,nb,6], mass, inertia [B,nb,3,3], restitution, fric,
         fext [B,nb,6], shape_type, shape_prm [B,nb,3], shape_aux [B,nb] (optional), mesh_id [B,nb], meshes [(verts, faces)...],
-        no_contact [nb,nb] (optional), Je [B,neq,6nb] (optional)."""
+        no_contact [nb,nb] (optional), Je [B,neq,6nb] (optional); with neural SDF bodies igr_net (igr.pack_weights) and, for
+        the network with a 4-number latent code, igr_latent [B,nb,4] (check_igr_spec)."""
         self.be = backend if backend is not None else TorchBackend()
         pose = np.asarray(spec["pose"], np.float64)
         B, nb = pose.shape[:2]
@@ -135,9 +162,9 @@ class BatchEngine:
         st_all = np.asarray(spec["shape_type"]).reshape(B, nb)
         igr_b = st_all == abi.SHAPE_IGR
         self.igr_items_cap = self.igr_qcap = 0
+        igr_latent = None
         if igr_b.any():
-            if spec.get("igr_net") is None:
-                raise ValueError("a body of shape_type SHAPE_IGR needs spec['igr_net'] (diffsdfsim_amd.igr.pack_weights)")
+            igr_latent = check_igr_spec(spec)
             nocon = np.asarray(spec.get("no_contact", np.zeros((nb, nb))), bool)
             per_scene = [sum(2 for i in range(nb) for j in range(i + 1, nb) if (row[i] or row[j]) and not nocon[i, j]) for row in igr_b]
             self.igr_items_cap = max(1, int(sum(per_scene)))
@@ -148,10 +175,6 @@ class BatchEngine:
         for name, shp in shapes.items():
             self.arr[name] = self.be.zeros(shp, abi.NP_DTYPE[kinds[name]])
         if igr_b.any():
-            from . import igr
-            if igr.packed_shape(spec["igr_net"]) != igr.SHAPES[0]:
-                raise NotImplementedError("the stepper carries 3 shape parameters per body (shape_prm): its neural bodies use the "
-                                          "5 -> 8 x 128 -> 1 network with a 2-number latent code")
             for k in abi.IGR_NET_POINTERS:
                 w = spec["igr_net"][k]
                 self.arr["igr_" + k] = w if not isinstance(w, np.ndarray) and hasattr(w, "data_ptr") else self.be.from_numpy(np.asarray(w, np.float64))
@@ -161,6 +184,9 @@ class BatchEngine:
                     shape_prm=spec["shape_prm"], mesh_id=spec["mesh_id"])
         if "shape_aux" in spec:
             host["shape_aux"] = spec["shape_aux"]
+        if igr_latent is not None:
+            shapes["igr_latent"] = (B, nb, abi.IGR_LATENT_MAX)
+            host["igr_latent"] = igr_latent
         host["no_contact"] = np.asarray(spec.get("no_contact", np.zeros((nb, nb))), np.uint8)
         if spec.get("grids"):      # voxel-grid SDF bodies: pooled table of their sample grids
             gs = [np.ascontiguousarray(np.asarray(g, np.float64)) for g in spec["grids"]]
@@ -193,9 +219,13 @@ class BatchEngine:
         W.shape_rare = int(bool(full))
         W.max_sub = max_sub
         W.igr_items_cap, W.igr_qcap, W.igr_rounds = self.igr_items_cap, self.igr_qcap, int(spec.get("igr_rounds", 0))
+        net_names = ["igr_" + k for k in abi.IGR_NET_POINTERS]
         for name, kind in abi.FIELDS:
-            if kind in ("pd", "pi", "pb"):
+            if kind in ("pd", "pi", "pb") and name not in net_names:
                 setattr(W, name, self.be.ptr(self.arr[name]) if name in self.arr else None)
+        if igr_b.any():
+            from . import igr
+            W.igr = abi.DssIgrNet(*[self.be.ptr(self.arr[n]) for n in net_names], *igr.packed_shape(spec["igr_net"]))
         # neural narrow phase: what the previous detection found (host side), which sizes the grids of the next one
         self.igr_hint = None
         if self.igr_items_cap > 0:
@@ -338,7 +368,8 @@ class BatchEngine:
     # -- backward ----------------------------------------------------------------------------------
     def _adjoint(self):
         if getattr(self, "adj", None) is None:
-            shp = abi.adjoint_shapes(self.B, self.nb, self.maxc, self.fd, int(self.arr["verts"].shape[0]), igr=self.igr_items_cap > 0)
+            shp = abi.adjoint_shapes(self.B, self.nb, self.maxc, self.fd, int(self.arr["verts"].shape[0]), igr=self.igr_items_cap > 0,
+                                     latent_table="igr_latent" in self.arr)
             kinds = dict(abi.ADJ_FIELDS)
             self.adj = {n: self.be.zeros(s, abi.NP_DTYPE[kinds[n]]) for n, s in shp.items()}
             A = abi.DssAdjoint()

@@ -231,7 +231,8 @@ def bounce_world_latent(latents, packed, use_toc_diff=True, use_friction=True, u
                         obj_pos=(0.0, 5.0, 0.0), obj_vel=(5.0, 0.0, 0.0), run_time=1.5, dt=Defaults3D.DT, res=128, device=None):
     """trajectory_fitting/optim_shapespace.py:90-124 for one scene per latent code: floor 50 x 1 x 50, wall [5,5,0] 1 x 10 x 10
     (pinned, no contact with each other), the neural-SDF body (scale 1, mass 1) at (0,5,0) thrown with (5,0,0); restitution
-    0.5, friction 0.25; no gravity by default, strict_no_penetration=False.  With `latents` a tensor that requires grad the
+    0.5, friction 0.25; no gravity by default, strict_no_penetration=False.  `latents` [B, 2] with a `packed` of the bob_spot
+    shape, [B, 4] with one of the shapenet shape (scenes.set_latents).  With `latents` a tensor that requires grad the
     scene is differentiable w.r.t. it three ways, as the reference's is: the SDF the contacts query, the level-set mesh
     (MeshSDF) the contact candidates come from, and the inertia integrated over that mesh."""
     lat_t = torch.as_tensor(latents, dtype=torch.float64)
@@ -272,7 +273,7 @@ def bounce_world_latent(latents, packed, use_toc_diff=True, use_friction=True, u
         spec["meshes"].append((v.detach().cpu().numpy(), f.cpu().numpy())); spec["mesh_vgrad"].append(np.zeros((v.shape[0], 3)))
         spec["mesh_id"][s, s_] = len(spec["meshes"]) - 1
         vts.append(v)
-    spec["shape_prm"][:, s_, :2] = lat
+    scenes.set_latents(spec, s_, lat, packed)
     spec["pose"][:, s_, 4:] = obj_pos
     spec["vel"][:, s_, 3:] = obj_vel
     spec["inertia"][:, s_] = torch.stack(Is).detach().numpy()
@@ -282,12 +283,14 @@ def bounce_world_latent(latents, packed, use_toc_diff=True, use_friction=True, u
         spec["fext"][:, s_, 4] = -10.0
     params = {}
     if lat_t.requires_grad:
-        prm = torch.tensor(spec["shape_prm"], dtype=torch.float64)
-        mine = torch.cat([lat_t.cpu(), torch.zeros(B, 1, dtype=torch.float64)], 1)[:, None]
+        # the code where the SDF queries read it: two numbers in the body's shape_prm row, four in its row of the latent table
+        key, width = ("igr_latent", abi.IGR_LATENT_MAX) if "igr_latent" in spec else ("shape_prm", 3)
+        prm = torch.tensor(spec[key], dtype=torch.float64)
+        mine = torch.cat([lat_t.cpu(), torch.zeros(B, width - lat.shape[1], dtype=torch.float64)], 1)[:, None]
         inertia = torch.tensor(spec["inertia"], dtype=torch.float64)
         dev = vts[-1].device
-        params = dict(shape_prm=torch.cat([prm[:, :s_], mine], 1), inertia=torch.cat([inertia[:, :s_], torch.stack(Is)[:, None]], 1),
-                      verts=torch.cat([v.to(dev) for v in vts]))
+        params = {key: torch.cat([prm[:, :s_], mine], 1), "inertia": torch.cat([inertia[:, :s_], torch.stack(Is)[:, None]], 1),
+                  "verts": torch.cat([v.to(dev) for v in vts])}
     steps = int(math.ceil(run_time / dt)) + 2
     return BatchWorld3D(spec, params=params, dt=dt, time_of_contact_diff=use_toc_diff, strict_no_penetration=False,
                         max_substeps=8 * steps + 64, device=device, maxc=256, max_cand=8192, max_pc=128)
@@ -455,8 +458,11 @@ def push_world(latents, packed, force, mass, fric, run_steps, floor_dims=(20.0, 
     """optim_sysid.py:104-131 (`make_world`) for one scene per latent code: the floor and a neural-SDF body (scale 1) set down
     on it (2 eps above, by its mesh's lowest vertex), gravity, a constant push (force[:, 0] along x, force[:, 1] along z),
     strict_no_penetration=False, fric_dirs=8.  `force` [B,2], `mass` [B], `fric` [B] (both bodies, as in the experiment) are
-    torch tensors and may require grad: the batch's parameters are built from them (inertia = mass x the mesh's unit inertia)."""
-    latents = np.asarray(latents, np.float64)
+    torch tensors and may require grad: the batch's parameters are built from them (inertia = mass x the mesh's unit inertia).
+    `latents` [B, 2] or, with a `packed` of the shapenet shape, [B, 4]; a tensor that requires grad makes the scene
+    differentiable w.r.t. it as bounce_world_latent's is (SDF queries, level-set mesh, inertia; the start pose is a constant)."""
+    lat_t = latents if torch.is_tensor(latents) and latents.requires_grad else None
+    latents = np.asarray(latents.detach().cpu() if torch.is_tensor(latents) else latents, np.float64)
     B, nb = latents.shape[0], 2
     spec, cache = scenes._base(B, nb), {}
     fd = np.asarray(floor_dims, np.float64)
@@ -465,10 +471,14 @@ def push_world(latents, packed, force, mass, fric, run_steps, floor_dims=(20.0, 
     spec["igr_net"] = packed
     spec["shape_type"][:, 1] = abi.SHAPE_IGR
     spec["shape_aux"][:, 1] = 1.0
-    Iunit = []
+    Iunit, vts = [], [torch.as_tensor(m[0], dtype=torch.float64) for m in spec["meshes"]]
     for s in range(B):
         key = tuple(latents[s])
-        if mesh_cache is None or key not in mesh_cache:
+        if lat_t is not None:
+            v, f = meshsdf.igr_mesh(lat_t[s].to(torch.float64), packed, res=res)
+            vts.append(v)
+            ent = (v.detach().cpu().numpy(), f.cpu().numpy(), mass_properties.mesh_inertia_diff(v, f, torch.tensor(1.0, dtype=torch.float64)).cpu())
+        elif mesh_cache is None or key not in mesh_cache:
             v, f = meshsdf.igr_mesh(torch.tensor(latents[s], dtype=torch.float64), packed, res=res)
             v = v.cpu().numpy(); f = f.cpu().numpy()
             ent = (v, f, np.asarray(mass_properties.mesh_inertia(v, f, 1.0).cpu()))
@@ -479,12 +489,12 @@ def push_world(latents, packed, force, mass, fric, run_steps, floor_dims=(20.0, 
         v, f, J = ent
         spec["meshes"].append((v, f)); spec["mesh_vgrad"].append(np.zeros_like(v))
         spec["mesh_id"][s, 1] = len(spec["meshes"]) - 1
-        spec["shape_prm"][s, 1, :2] = latents[s]
         spec["pose"][s, 1, 4:] = (0.0, -v[:, 1].min() + 2 * Defaults3D.EPSILON, 0.0)
         Iunit.append(J)
+    scenes.set_latents(spec, 1, latents, packed)      # ([B, 2] or, with the shapenet network, [B, 4])
     T = lambda x: torch.as_tensor(x, dtype=torch.float64)
     mass, fric, force = T(mass), T(fric), T(force)
-    Iu = T(np.stack(Iunit))
+    Iu = torch.stack(Iunit) if lat_t is not None else T(np.stack(Iunit))
     one = torch.ones(B, dtype=torch.float64)
     zero = torch.zeros(B, dtype=torch.float64)
     params = dict(
@@ -494,6 +504,11 @@ def push_world(latents, packed, force, mass, fric, run_steps, floor_dims=(20.0, 
         fext=torch.stack([torch.zeros(B, 6, dtype=torch.float64), torch.stack([zero, zero, zero, force[:, 0], -g * mass, force[:, 1]], 1)], 1))
     for k in ("mass", "inertia", "fric", "fext"):
         spec[k] = params[k].detach().numpy()
+    if lat_t is not None:
+        key, width = ("igr_latent", abi.IGR_LATENT_MAX) if "igr_latent" in spec else ("shape_prm", 3)
+        rows = torch.cat([lat_t.cpu().to(torch.float64), torch.zeros(B, width - latents.shape[1], dtype=torch.float64)], 1)
+        params[key] = torch.stack([T(spec[key][:, 0]), rows], 1)
+        params["verts"] = torch.cat([v.to(vts[-1].device) for v in vts])
     w = BatchWorld3D(spec, params=params, strict_no_penetration=False, max_substeps=4 * run_steps + 64, device=device,
                      maxc=256, max_cand=8192, max_pc=128)
     return w
@@ -551,7 +566,7 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--net", default="bob_spot", choices=["bob_spot", "shapenet"],
-                    help="inertia: the network shape (bob_spot: latent 2, 8 x 128; shapenet: latent 4, 8 x 256)")
+                    help="shapespace, sysid, inertia: the network shape (bob_spot: latent 2, 8 x 128; shapenet: latent 4, 8 x 256)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     r = np.random.default_rng(a.seed)
@@ -567,8 +582,9 @@ def main(argv=None):
             np.savez_compressed(a.out, **{k.replace(" ", "_").replace(",", ""): v["radius"] for k, v in res.items()}, target=target, start=start)
     elif a.what == "shapespace":
         from . import igr
-        packed = igr.pack_weights(*scenes.geometric_init_weights(a.seed, 0.5))
-        tgt, st = 0.1 * r.standard_normal((a.scenes, 2)), 0.1 * r.standard_normal((a.scenes, 2))
+        width, nlat = igr.SHAPES[a.net == "shapenet"]
+        packed = igr.pack_weights(*scenes.geometric_init_weights(a.seed, 0.5, width, nlat))
+        tgt, st = 0.1 * r.standard_normal((a.scenes, nlat)), 0.1 * r.standard_normal((a.scenes, nlat))
         res = fit_trajectory_latent(tgt, st, packed, run_time=a.run_time, max_iter=a.iters, log=print)
         print("shapespace: mean loss %.3e -> %.3e, %d scenes" % (float(res["history"][0]["loss"].mean()), float(res["history"][-1]["loss"].mean()), a.scenes))
     elif a.what == "primitives":
@@ -582,9 +598,10 @@ def main(argv=None):
     elif a.what == "sysid":
         # optim_sysid.py:184-220: a random latent, push, mass and friction per scene; the goal's start value is drawn anew
         from . import igr
-        packed = igr.pack_weights(*scenes.geometric_init_weights(a.seed, 0.5))
+        width, nlat = igr.SHAPES[a.net == "shapenet"]
+        packed = igr.pack_weights(*scenes.geometric_init_weights(a.seed, 0.5, width, nlat))
         uni = lambda lo, hi, *sh: lo + (hi - lo) * r.random((a.scenes,) + sh)
-        lat = 0.1 * r.standard_normal((a.scenes, 2))
+        lat = 0.1 * r.standard_normal((a.scenes, nlat))
         target = dict(force=uni(2.0, 5.0, 2), mass=uni(0.9, 1.1), fric=uni(0.01, 0.25))
         start = dict(force=uni(2.0, 5.0, 2), mass=uni(0.9, 1.1), fric=uni(0.01, 0.25))
         res = fit_sysid(a.goal, lat, packed, target, start, run_time=a.run_time, max_iter=a.iters, log=print)

@@ -18,20 +18,24 @@ from .. import world_abi as abi
 from ..engine import BatchEngine, TorchBackend
 from .utils import Defaults3D
 
-PARAMS = ("mass", "inertia", "restitution", "fric", "fext", "shape_prm")
+# differentiable per-body inputs of a step; igr_latent (the latent table of neural bodies on the network with a 4-number
+# code, [B,nb,4]) exists only in a world whose engine was given spec["igr_latent"]
+PARAMS = ("mass", "inertia", "restitution", "fric", "fext", "shape_prm", "igr_latent")
 
 
 class _StepFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, world, fixed_dt, pose, vel, mass, inertia, rest, fric, fext, prm, verts=None, mask=None, nsteps=1):
+    def forward(ctx, world, fixed_dt, pose, vel, mass, inertia, rest, fric, fext, prm, verts=None, mask=None, nsteps=1, latent=None):
         # verts: the mesh table's vertices [NV,3] as a differentiable input (level-set meshes: their shape gradient flows
         # through the vertex positions); the engine already holds their values, only the adjoint is produced
         E = world.engine
-        ctx.has_verts = verts is not None
+        ctx.has_verts, ctx.has_latent = verts is not None, latent is not None
         # upload only what changed since the last step: parameters are usually the same tensors all along, and the
         # state handed in is usually the very tensor the previous step handed out (the engine still holds its values)
         seen = world.__dict__.setdefault("_uploaded", {})
-        for name, t in zip(("pose", "vel") + PARAMS, (pose, vel, mass, inertia, rest, fric, fext, prm)):
+        for name, t in zip(("pose", "vel") + PARAMS, (pose, vel, mass, inertia, rest, fric, fext, prm, latent)):
+            if t is None:
+                continue
             hit = seen.get(name)      # (tensor, version): the reference keeps the tensor alive, so `is` cannot be fooled by id reuse
             if hit is not None and hit[0] is t and hit[1] == t._version:
                 continue
@@ -107,7 +111,7 @@ class _StepFn(torch.autograd.Function):
             else:
                 ctx_saved = None
         w._bw_next = ctx.index - 1
-        for k in ("g_mass", "g_inertia", "g_rest", "g_fric", "g_fext", "g_prm", "g_verts"):
+        for k in ("g_mass", "g_inertia", "g_rest", "g_fric", "g_fext", "g_prm", "g_verts") + (("g_latent",) if ctx.has_latent else ()):
             adj[k].zero_()
         E.A.g_verts = E.be.ptr(adj["g_verts"]) if ctx.has_verts else None
         adj["a_pose"].copy_(g_pose)
@@ -136,7 +140,8 @@ class _StepFn(torch.autograd.Function):
             adj["a_last_dt"][off] += al
         return (None, None, adj["a_pose"].clone(), adj["a_vel"].clone(), adj["g_mass"].clone(),
                 adj["g_inertia"].reshape(E.B, E.nb, 3, 3).clone(), adj["g_rest"].clone(), adj["g_fric"].clone(),
-                adj["g_fext"].clone(), adj["g_prm"].clone(), adj["g_verts"].clone() if ctx.has_verts else None, None, None)
+                adj["g_fext"].clone(), adj["g_prm"].clone(), adj["g_verts"].clone() if ctx.has_verts else None, None, None,
+                adj["g_latent"].clone() if ctx.has_latent else None)
 
 
 class BatchWorld3D:
@@ -144,7 +149,8 @@ class BatchWorld3D:
 
     ``spec``: BatchEngine spec (see diffsdfsim_amd.scenes).  ``params``: optional dict of torch tensors
     (mass [B,nb], inertia [B,nb,3,3], restitution, fric [B,nb], fext [B,nb,6], shape_prm [B,nb,3]; optionally verts
-    [NV,3], the pooled mesh vertices, for shape gradients through level-set meshes) that may require grad; ``pose`` / ``vel`` are the current state tensors (autograd-connected)."""
+    [NV,3], the pooled mesh vertices, for shape gradients through level-set meshes, and igr_latent [B,nb,4], the latent table
+    of a spec with spec["igr_latent"]) that may require grad; ``pose`` / ``vel`` are the current state tensors (autograd-connected)."""
 
     def __init__(self, spec, params=None, dt=Defaults3D.DT, eps=Defaults3D.EPSILON, tol=Defaults3D.TOL,
                  fric_dirs=Defaults3D.FRIC_DIRS, strict_no_penetration=True, time_of_contact_diff=True, device=None,
@@ -160,8 +166,10 @@ class BatchWorld3D:
         E = self.engine
         self.device, self.dt = dev, dt
         self.B, self.nb = E.B, E.nb
-        self.params = {k: E.arr[k].clone().reshape((E.B, E.nb, 3, 3) if k == "inertia" else E.arr[k].shape) for k in PARAMS}
+        self.params = {k: E.arr[k].clone().reshape((E.B, E.nb, 3, 3) if k == "inertia" else E.arr[k].shape) for k in PARAMS if k in E.arr}
         for k, v in (params or {}).items():
+            if k == "igr_latent" and k not in E.arr:
+                raise ValueError("params['igr_latent'] needs a spec with spec['igr_latent'] (the network with a 4-number latent code)")
             self.params[k] = v
         self.pose, self.vel = E.arr["pose"].clone(), E.arr["vel"].clone()
         self._n_nodes, self._bw_next = 0, -1
@@ -200,7 +208,8 @@ class BatchWorld3D:
         outs = _StepFn.apply(self, fixed_dt, to("pose", self.pose), to("vel", self.vel), to("mass", P["mass"]),
                              to("inertia", P["inertia"]), to("restitution", P["restitution"]), to("fric", P["fric"]),
                              to("fext", P["fext"]), to("shape_prm", P["shape_prm"]),
-                             to("verts", P["verts"]) if P.get("verts") is not None else None, mask, nsteps)
+                             to("verts", P["verts"]) if P.get("verts") is not None else None, mask, nsteps,
+                             to("igr_latent", P["igr_latent"]) if P.get("igr_latent") is not None else None)
         self.pose, self.vel = outs[0], outs[1]
         # (record_substeps: the entries of the sub-steps inside this call -- poses / velocities [K, B, ...] with their graph, start
         # times [K, B], validity [K, B] -- and the start time of the last sub-step, whose entry is (self.pose, self.vel))

@@ -113,11 +113,27 @@ def sphere_drop(B, seed=0, floor_dims=(20.0, 1.0, 20.0), mu=0.25, rest=0.5, g=10
     return spec
 
 
+def set_latents(spec, body, latents, packed):
+    """Put the latent codes `latents` [B, L] of neural body `body` where the stepper reads them for the network of `packed`:
+    a 2-number code in shape_prm[:, body, :2], a 4-number code in the latent table spec['igr_latent'] [B, nb, 4]."""
+    from . import igr
+    latents = np.asarray(latents, np.float64)
+    nlat = igr.packed_shape(packed)[1]
+    if latents.ndim != 2 or latents.shape[1] != nlat:
+        raise ValueError("latent codes of shape %s for a network with a %d-number latent code" % (latents.shape, nlat))
+    if nlat <= 2:
+        spec["shape_prm"][:, body, :nlat] = latents
+    else:
+        B, nb = spec["pose"].shape[:2]
+        spec.setdefault("igr_latent", np.zeros((B, nb, abi.IGR_LATENT_MAX)))[:, body, :nlat] = latents
+
+
 def igr_pole(B, seed=0, packed=None, radius_init=0.5, latent_sigma=0.1, y0=6.0, res=128, mu=0.15, g=10.0, floor_dims=(50.0, 1.0, 50.0)):
     """config 4 (BASELINE configs[3]): ``demos/demo_meshsdf.make_world`` (demo_meshsdf.py:121-142) for a batch -- level-set floor
     50 x 1 x 50, pinned cylinder pole (r 0.2, h 2, upright at x = 0.35, no contact with the floor), one neural-SDF body of scale
     2 per scene dropped from y = 6 with its own latent code ~ N(0, sigma^2).  The trained IGR weights are not available
-    offline: ``packed`` defaults to seeded geometric-init weights of the bob_spot_setup shape (synthetic, like all data here).
+    offline: ``packed`` defaults to seeded geometric-init weights of the bob_spot_setup shape (synthetic, like all data here);
+    a ``packed`` of the shapenet shape (latent 4, 8 x 256) gives every body a 4-number code in spec['igr_latent'].
     Needs the HIP device: the level-set meshes and their inertias are built by the device operators."""
     import torch
     from . import igr, mass_properties, meshsdf
@@ -155,17 +171,19 @@ def igr_pole(B, seed=0, packed=None, radius_init=0.5, latent_sigma=0.1, y0=6.0, 
     spec["mesh_id"][:, 1] = 1
     spec["shape_type"][:, 2] = abi.SHAPE_IGR
     spec["shape_aux"][:, 2] = 2.0
+    nlat = igr.packed_shape(packed)[1]
+    lats = np.zeros((B, nlat))
     for s in range(B):
-        lat = latent_sigma * r.standard_normal(2)
+        lat = lats[s] = latent_sigma * r.standard_normal(nlat)
         v, f = meshsdf.igr_mesh(torch.tensor(lat, dtype=torch.float64), packed, res=res)
         v = (v * 2.0).cpu().numpy(); f = f.cpu().numpy()
         spec["meshes"].append((v, f)); spec["mesh_vgrad"].append(np.zeros_like(v))
         spec["mesh_id"][s, 2] = 2 + s
-        spec["shape_prm"][s, 2, :2] = lat
         spec["inertia"][s, 2] = np.asarray(mass_properties.mesh_inertia(v, f, 1.0).cpu())
         spec["pose"][s, 2, 4:] = (0.0, y0, 0.0)
         spec["fric"][s, 2] = mu
         spec["fext"][s, 2, 4] = -g
+    set_latents(spec, 2, lats, packed)
     return spec
 
 

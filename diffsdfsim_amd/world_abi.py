@@ -10,12 +10,13 @@ import ctypes
 import numpy as np
 
 # the header's #defines (DSS_<name>)
-ABI_VERSION = 3
+ABI_VERSION = 4
 CAND_FIELDS = 28
 CSCR_ROWS = 56
 N_ACTIVE_OVERFLOW = 1 << 30
 SHAPE_BOX, SHAPE_SPHERE, SHAPE_CYLINDER, SHAPE_BOX_ROUNDED, SHAPE_BRICK, SHAPE_BOWL, SHAPE_IGR, SHAPE_GRID = 0, 1, 2, 3, 4, 5, 6, 7
 IGR_HDR, IGR_ROUNDS = 16, 42
+IGR_LATENT_MAX = 4
 
 _I, _D, _P = ctypes.c_int, ctypes.c_double, ctypes.c_void_p
 
@@ -99,19 +100,37 @@ FIELDS = [
     ("igr_list", "pi"), ("igr_hdr", "pi"), ("igr_cface", "pi"), ("igr_cstate", "pi"), ("igr_cbuf", "pd"),
     ("igr_qpts", "pd"), ("igr_qlat", "pi"), ("igr_qtag", "pi"), ("igr_qsdf", "pd"), ("igr_qgrad", "pd"), ("igr_qn", "pi"),
     ("igr_hint", "ev"), ("igr_ev", "ev"),
+    ("igr_latent", "pd"),
 ]
 
 
+def _world_fields():
+    """ctypes fields of DssWorld: FIELDS in order, with the members of `DssIgrNet igr` (listed there as igr_<member>, as the
+    header's text reads) as ONE nested struct `igr`: W.igr.latent is the network's latent size, W.igr_latent the latent table."""
+    i0 = FIELDS.index(("igr_" + IGR_NET_FIELDS[0], "pd"))
+    flat = [(n, {"i": _I, "d": _D}.get(k, _P)) for n, k in FIELDS]
+    return flat[:i0] + [("igr", DssIgrNet)] + flat[i0 + len(IGR_NET_FIELDS):]
+
+
 class DssWorld(ctypes.Structure):
-    _fields_ = [(n, {"i": _I, "d": _D}.get(k, _P)) for n, k in FIELDS]
+    _fields_ = _world_fields()
 
 
 NP_DTYPE = {"pd": np.float64, "pi": np.int32, "pb": np.uint8}
 
 
-def igr_shapes(items_cap, qcap, max_cand):
-    """Arrays of the round-based narrow phase for neural SDF bodies (narrowphase_igr.hip)."""
+def igr_shapes(items_cap, qcap, max_cand, B=None, nb=None, maxc=None):
+    """Arrays of the round-based narrow phase for neural SDF bodies (narrowphase_igr.hip); with B, nb and maxc also the
+    latent table and what the reverse sweep adds for such bodies (step_bwd.hip): igr_bw_grad holds d phi / d xyz [cap][3]
+    followed by d phi / d latent in rows of three (the two-number code) or of IGR_LATENT_MAX (the four-number code), so it
+    is sized for the wider of the two."""
+    extra = {}
+    if B is not None:
+        cap = B * 2 * maxc
+        extra = {"igr_latent": (B, nb, IGR_LATENT_MAX), "g_latent": (B, nb, IGR_LATENT_MAX), "igr_bw_n": (1,), "igr_bw_idx": (B, 2, maxc),
+                 "igr_bw_pts": (cap, 3), "igr_bw_lat": (cap,), "igr_bw_sdf": (2, cap), "igr_bw_grad": (cap * (3 + IGR_LATENT_MAX),)}
     return {
+        **extra,
         "igr_list": (items_cap,), "igr_hdr": (items_cap, IGR_HDR), "igr_cface": (items_cap, 3, max_cand),
         "igr_cstate": (items_cap, max_cand), "igr_cbuf": (items_cap, CAND_FIELDS, max_cand),
         "igr_qpts": (4, qcap, 3), "igr_qlat": (4, qcap), "igr_qtag": (4, qcap), "igr_qsdf": (4, qcap), "igr_qgrad": (2, qcap, 3),
@@ -160,6 +179,7 @@ ADJ_FIELDS = [
     ("cur_slot", "pi"), ("lo_slot", "pi"), ("bw_active", "pi"),
     ("a_x", "pd"), ("dMblk", "pd"), ("dpvec", "pd"), ("dcop", "pd"), ("cscr", "pd"), ("bw_nc", "pi"),
     ("igr_bw_n", "pi"), ("igr_bw_idx", "pi"), ("igr_bw_pts", "pd"), ("igr_bw_lat", "pi"), ("igr_bw_sdf", "pd"), ("igr_bw_grad", "pd"),
+    ("g_latent", "pd"),
 ]
 
 
@@ -167,11 +187,12 @@ class DssAdjoint(ctypes.Structure):
     _fields_ = [(n, _P) for n, k in ADJ_FIELDS]
 
 
-def adjoint_shapes(B, nb, maxc, fd, NV=1, igr=False):
+def adjoint_shapes(B, nb, maxc, fd, NV=1, igr=False, latent_table=False):
+    """Arrays of DssAdjoint; igr: the scratch of the neural bodies' records, latent_table: g_latent (DssWorld.igr_latent is set)."""
     NFc = 3 * (1 + fd // 2) + 8
-    cap = B * 2 * maxc
-    extra = {"igr_bw_n": (1,), "igr_bw_idx": (B, 2, maxc), "igr_bw_pts": (cap, 3), "igr_bw_lat": (cap,), "igr_bw_sdf": (2, cap),
-             "igr_bw_grad": (2, cap, 3)} if igr else {}
+    names = [n for n, _k in ADJ_FIELDS if n.startswith("igr_bw_")] * bool(igr) + ["g_latent"] * bool(latent_table)
+    every = igr_shapes(1, 1, 1, B, nb, maxc)
+    extra = {n: every[n] for n in names}
     return {
         **extra,
         "a_pose": (B, nb, 7), "a_vel": (B, nb, 6), "a_geom": (B, 10, maxc), "a_last_dt": (B,), "a_dt": (B,),

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DSS_ABI_VERSION 3
+#define DSS_ABI_VERSION 4
 
 /* return codes of the launchers */
 #define DSS_OK 0
@@ -115,7 +115,8 @@ int dss_lcp_contact_backward(const double *Mblk, const double *A, const double *
  * W0 [H][L + 3], b0 [H]; Wp = the seven H x H layers in MFMA fragment order ([7][H/16][H/4][64] doubles,
  * diffsdfsim_amd/igr.py: pack_weights; layer 3's L + 3 missing rows are zero), bh [7][H]; W8 [H], b8 [1].
  * Built: (H, L) = (128, 2), bob_spot_setup.conf, and (256, 4), shapenet.conf; 0 in both fields means (128, 2).  The stepper
- * (DssWorld.igr) runs the (128, 2) network only: shape_prm carries three numbers per body. */
+ * (DssWorld.igr) runs both: the (128, 2) network reads its latent code from shape_prm[0..1], the (256, 4) network from the
+ * latent table DssWorld.igr_latent (shape_prm carries three numbers per body). */
 typedef struct DssIgrNet {
     const double *W0, *b0, *Wp, *bh, *W8, *b8;
     int width;    /* H: 128 or 256 (0 = 128) */
@@ -219,7 +220,7 @@ typedef struct DssWorld {
     void *ev_lcp_start, *ev_lcp_stop;
     void *ev_np_start, *ev_np_stop;   /* same, around the contact-detection launches */
     /* ---- neural SDF bodies (shape_type DSS_SHAPE_IGR; SDF3D(sdf_func=decode_igr(net), params=[latent]), bodies.py:627-760):
-       shape_prm[0..1] = the body's latent code, shape_aux = its scale.  A directed pair with a neural body is a work item of
+       shape_prm[0..1] = the body's latent code (or a row of igr_latent, below), shape_aux = its scale.  A directed pair with a neural body is a work item of
        the round-based narrow phase (narrowphase_igr.hip): items advance from one batch of SDF queries to the next, the
        queries of all items are evaluated together on the matrix cores (igr_mlp.hip).  All NULL / 0 without such bodies. */
     DssIgrNet igr;
@@ -243,6 +244,9 @@ typedef struct DssWorld {
                                 whatever the device-side lengths turn out to be.  NULL = grids that fill the chip. */
     void **igr_ev;           /* optional hipEvent_t [4 (DSS_IGR_ROUNDS + 1)] in HOST memory: (start, stop) around the value-list and the
                                 gradient-list evaluation of every round (bench roofline); NULL in production */
+    const double *igr_latent; /* optional [B][nb][DSS_IGR_LATENT_MAX]: row scene * nb + body = the latent code of a neural body (rows of
+                                other bodies are ignored).  NULL = the code is shape_prm[0..1] (stride 3).  Required when igr.latent > 3:
+                                dss_find_contacts / dss_step_attempt / dss_step_backward return DSS_E_BADARG without it */
 } DssWorld;
 
 #define DSS_GRAD_STOP_CONTACT 1    /* stop_contact_grad: Jc (and h = Jc v) from detached contact geometry, world.py:59-62 */
@@ -260,8 +264,9 @@ typedef struct DssWorld {
 #define DSS_SHAPE_BRICK 4      /* SDFBrick (bodies.py:873-885): shape_prm = dims, shape_aux = r (x-y corners rounded) */
 #define DSS_SHAPE_BOWL 5       /* SDFBowl (bodies.py:1013-1027): shape_prm = (r, d, -), opening towards +z */
 #define DSS_SHAPE_GRID 7       /* SDFGrid3D (bodies.py:763-775): samples of the SDF over the body's unit cube, shape_aux = scale */
-#define DSS_SHAPE_IGR 6        /* SDF3D with decode_igr (bodies.py:627-760, utils.py:330-350): shape_prm = latent code (2), shape_aux = scale */
+#define DSS_SHAPE_IGR 6        /* SDF3D with decode_igr (bodies.py:627-760, utils.py:330-350): shape_prm = latent code (2) unless DssWorld.igr_latent holds it, shape_aux = scale */
 #define DSS_IGR_HDR 16         /* ints of per-item state of the round-based narrow phase */
+#define DSS_IGR_LATENT_MAX 4   /* numbers per row of DssWorld.igr_latent / DssAdjoint.g_latent */
 #define DSS_IGR_ROUNDS 42      /* query rounds that cover every stage: candidates 2, Frank-Wolfe 1 + 31, projection 2, geometry 4, spare */
 
 size_t dss_world_sizeof(void);   /* sizeof(DssWorld): lets a binding check its mirror struct */
@@ -316,7 +321,11 @@ typedef struct DssAdjoint {
     double *igr_bw_pts;      /* [B 2 maxc][3] */
     int *igr_bw_lat;         /* [B 2 maxc] */
     double *igr_bw_sdf;      /* [2][B 2 maxc] phi from the xyz pass / the latent pass */
-    double *igr_bw_grad;     /* [2][B 2 maxc][3] d phi / d xyz, d phi / d latent */
+    double *igr_bw_grad;     /* [B 2 maxc][3] d phi / d xyz, then [B 2 maxc][3] d phi / d latent -- [B 2 maxc][4] for a network with
+                                igr.latent > 3 (DSS_IGR_LATENT fills four columns): B 2 maxc (3 + DSS_IGR_LATENT_MAX) doubles hold either */
+    double *g_latent;        /* [B][nb][DSS_IGR_LATENT_MAX] d(loss)/d(igr_latent), accumulated where g_prm is; required exactly when
+                                DssWorld.igr_latent is set (dss_step_backward: DSS_E_BADARG otherwise), and g_prm rows of neural
+                                bodies then stay zero */
 } DssAdjoint;
 
 size_t dss_adjoint_sizeof(void);
