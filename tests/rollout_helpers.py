@@ -130,18 +130,101 @@ def check_gradients(E, g, tol=1e-5, s=0, branch_tol=1e-5):
     return which, errs
 
 
-def rollout_and_sweep(E, nsteps):
+def position_seed(pose, vel):
+    """The incoming adjoint of sum |pos_T|^2: 2 pos in the position rows, nothing in the quaternion rows or on the velocity."""
+    ap = np.zeros_like(pose)
+    ap[:, :, 4:] = 2 * pose[:, :, 4:]
+    return ap, np.zeros_like(vel)
+
+
+def rollout_and_sweep(E, nsteps, seed=None):
+    """`nsteps` outer steps, then the reverse sweep over the whole tape.  `seed(pose_T, vel_T) -> (a_pose, a_vel)` gives the
+    incoming adjoint d loss / d (final pose [B,nb,7], final velocity [B,nb,6]); default: that of sum |pos_T|^2."""
     for _ in range(nsteps):
         E.step()
     adj = E._adjoint()
-    ap = np.zeros_like(E.get("pose"))
-    ap[:, :, 4:] = 2 * E.get("pose")[:, :, 4:]     # d/dpos of sum |pos|^2
+    ap, av = (seed or position_seed)(E.get("pose"), E.get("vel"))
     adj["a_pose"][...] = E.be.from_numpy(ap)
+    adj["a_vel"][...] = E.be.from_numpy(av)
     adj["cur_slot"][...] = E.be.from_numpy((E.get("nsub") - 1).astype(np.int32))
     adj["lo_slot"][...] = -1      # down to and including the contacts found at construction
     E.backward_sweep(int(E.get("nsub").max()) + 1)
 
 
+# ---- every output of the reverse sweep against the reference's leaves (tests/golden/rollout_general_*.npz,
+#      oracle/gen/gen_general_golden.py) ----
+def general_seed(g, part=""):
+    """The incoming adjoint of the goldens' terminal loss sum_b cp_b . p_b + cv_b . v_b + 0.5 |p_b|^2 over the moving bodies
+    (cp, cv: `loss_cp`, `loss_cv`; zero rows for pinned bodies).  part = 'quatonly_': the quaternion rows of it alone;
+    'velonly_': the velocity rows alone."""
+    cp, cv = g["loss_cp"], g["loss_cv"]
+    mv = np.array([b not in g["fixed"] for b in range(len(g["mass"]))], float)[None, :, None]
+
+    def seed(pose, vel):
+        ap, av = (cp[None] + pose) * mv, np.broadcast_to(cv[None], vel.shape) * mv
+        if part == "quatonly_":
+            ap[:, :, 4:] = 0.0
+            av = np.zeros_like(vel)
+        elif part == "velonly_":
+            ap = np.zeros_like(pose)
+        return ap, av
+    return seed
+
+
+def leaf_grads(E, g, s=0):
+    """The reference's leaves {name: gradient} from the sweep's outputs for scene `s`, after the sweep has run down to slot -1:
+    rest_<b> = g_rest, fric_<b> = g_fric, wrench_<b> = g_fext (the wrench adds to the external force one to one),
+    pose_<b> / vel_<b> = a_pose / a_vel (by then d loss / d start state), shape_<i> = param_grads (g_prm with g_inertia chained
+    onto dims / radius / height).
+    mass_<b>: the engine's inputs mass, inertia and fext are independent of each other, and g_mass holds the derivative through
+    the explicit m alone -- the linear block of M in u = M v + dt f and in the LCP's mass matrix (step_bwd.hip, bwd_post_kernel)
+    and the acceleration f/m of a time-of-contact event (bwd_pre_kernel).  It does NOT contain gravity: the spec's fext
+    already is wrench + m g (0, -1, 0) and the kernels never form m g.  The reference's mass leaf also scales the custom inertia
+    (J = m f(shape), bodies.py:796-797, 910-912, 970-971) and the weight, so both chains are added here."""
+    adj = {k: E.be.to_numpy(v) for k, v in E.adj.items()}
+    out = {}
+    for b in range(len(g["mass"])):
+        m = g["mass"][b]
+        out["mass_%d" % b] = np.asarray(adj["g_mass"][s, b] + (adj["g_inertia"][s, b].reshape(3, 3) * g["inertia"][b]).sum() / m
+                                        - float(g["gravity"]) * adj["g_fext"][s, b, 4])
+        out["fric_%d" % b] = np.asarray(adj["g_fric"][s, b])
+        out["rest_%d" % b] = np.asarray(adj["g_rest"][s, b])
+        if b not in g["fixed"]:
+            out["wrench_%d" % b] = adj["g_fext"][s, b].copy()
+            out["pose_%d" % b] = adj["a_pose"][s, b].copy()
+            out["vel_%d" % b] = adj["a_vel"][s, b].copy()
+    for i, gi in enumerate(param_grads(E, g, s)):
+        out["shape_%d" % i] = np.asarray(gi)
+    return out
+
+
+def leaf_errors(got, g, run="A", part="", floor=1e-9):
+    """Per compared leaf: max |got - want| / max |want| over the components whose reference magnitude is at least `floor`.
+    Leaves the golden lists as structurally dead (`dead_leaves`: the pinned floor's mass, for which the reference's graph
+    returns rounding residue of 1e-40) are not compared; every other leaf of the golden must be present in `got`."""
+    errs = {}
+    for name in g["leaves"]:
+        name = str(name)
+        want = np.asarray(g[("grad_" if run == "A" else "gradB_") + part + name], float)
+        if name in g["dead_leaves"]:
+            continue
+        mine = np.asarray(got[name], float).reshape(want.shape)
+        keep = np.abs(want) >= floor
+        assert keep.any(), (name, "no component of this leaf carries a gradient: the scene does not test it")
+        errs[name] = float(np.abs(mine - want)[keep].max() / np.abs(want).max())
+    return errs
+
+
+def check_general(E, g, s=0, part="", tol=1e-5):
+    """The branch run the build reproduced (required to be identifiable: 'A' or 'B') and every leaf against that run's
+    gradient to `tol` relative to the leaf's largest reference component (north star / check_gradients' branch_tol)."""
+    which = check_branches_and_pick_reference(E, g, s)
+    assert which in ("A", "B"), "the build's normal choices equal neither recorded run of the reference"
+    errs = leaf_errors(leaf_grads(E, g, s), g, which, part)
+    print("%s leaf errors vs run %s: %s" % (part or "general", which, ", ".join("%s %.1e" % kv for kv in sorted(errs.items()))))
+    bad = {k: e for k, e in errs.items() if not e < tol}
+    assert not bad, (which, bad)
+    return which, errs
 
 
 def _quat_to_mat(q):

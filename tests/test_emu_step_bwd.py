@@ -1,5 +1,6 @@
 """CPU: reverse sweep of the stepper (csrc/step_bwd.hip) in the fiber emulator against the gradients
-torch.autograd produced for the reference rollouts (tests/golden/rollout_*.npz: grad of sum |pos_T|^2)."""
+torch.autograd produced for the reference rollouts (tests/golden/rollout_*.npz: grad of sum |pos_T|^2 w.r.t. the shape;
+rollout_general_*.npz: grad of a loss on every row of the final pose and velocity w.r.t. every physical leaf)."""
 import numpy as np
 import pytest
 
@@ -15,3 +16,18 @@ def test_gradients_match_reference_autograd(name, nsteps):
     R.rollout_and_sweep(E, nsteps)
     # two boxes: several independent coin flips, the two recorded branches differ by 3e-4
     R.check_gradients(E, g, tol=1e-3 if name == "rollout_stack2" else 1e-5)
+
+
+@pytest.mark.parametrize("name,nsteps", [("rollout_general_boxdrop", 12), ("rollout_general_sphere_notoc", 24)])
+def test_every_leaf_matches_reference_autograd(name, nsteps):
+    """The assertions of tests/test_step_general_grad_gpu.py where there is no GPU: mass, friction and restitution of every
+    body, start pose and velocity, the wrench and the shape, 1e-5 relative per leaf against the reference run the build
+    reproduced; sub-step count exact, final state 1e-8."""
+    g = R.load_rollout(name)
+    E = BatchEngine(R.spec_from_golden(g), backend=emu.EmuBackend(), max_sub=64, **R.engine_kwargs(g))
+    R.rollout_and_sweep(E, nsteps, R.general_seed(g))
+    assert (E.get("nsub") == len(g["traj_t"])).all()
+    k = len(g["traj_t"]) - 1
+    assert np.abs(E.get("pose")[0] - g["traj_p"][k]).max() < 1e-8 and np.abs(E.get("vel")[0] - g["traj_v"][k]).max() < 1e-8
+    assert bool((E.get("tp_flags") & 1).any()) == (name == "rollout_general_boxdrop"), "time-of-contact events: with toc_diff only"
+    R.check_general(E, g)
