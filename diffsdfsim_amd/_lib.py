@@ -69,8 +69,10 @@ def build(force=False, verbose=False, diag=False):
         obj = os.path.join(objdir, name[:-4] + ".o")
         objs.append(obj)
         dep = os.path.getmtime(src)
-        if name.endswith("_all.hip"):      # second compilation of <base>.hip with every primitive SDF (see narrowphase.hip)
-            dep = max(dep, os.path.getmtime(os.path.join(CSRC, name[:-8] + ".hip")))
+        # further compilations of <base>.hip: with every primitive SDF / for batches made only of boxes (see narrowphase.hip)
+        for suffix in ("_all.hip", "_box.hip"):
+            if name.endswith(suffix):
+                dep = max(dep, os.path.getmtime(os.path.join(CSRC, name[:-len(suffix)] + ".hip")))
         if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(dep, hnew):
             continue
         # -cuid=<file stem>: the compilation-unit id is otherwise hashed from the source's absolute path; with a fixed one the

@@ -7,6 +7,8 @@
 namespace dss {
 #if DSS_ALL_SHAPES
 inline namespace shapes_all {
+#elif DSS_BOX_ONLY
+inline namespace shapes_box {
 #else
 inline namespace shapes_lean {
 #endif

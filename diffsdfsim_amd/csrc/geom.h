@@ -293,15 +293,31 @@ template <class T> __host__ __device__ inline void world_inertia(const T *q, con
 // ---- primitive SDFs (physics3d/bodies.py:38-185) and SDF3D.query_sdfs (:721-760) ------------
 // The stepper's two hot kernels (narrow phase, contact adjoint) are compiled twice: a lean variant that knows only box /
 // sphere / cylinder (DSS_ALL_SHAPES 0: the remaining primitives cost it registers it does not have) and a variant with
-// every primitive, picked at launch by DssWorld.shape_rare.  The shape code sits in an inline namespace per variant, so
-// the two sets of inline functions are distinct entities.
+// every primitive, picked at launch by DssWorld.shape_rare.  The narrow phase has a third compilation for batches whose
+// every body is a box (DSS_ALL_SHAPES 0 with DSS_BOX_ONLY 1, picked by DssWorld.shape_box): the preprocessor leaves the
+// box statements of the lean set, word for word, and nothing else.  The shape code sits in an inline namespace per
+// variant, so the sets of inline functions are distinct entities.
 #ifndef DSS_ALL_SHAPES
 #define DSS_ALL_SHAPES 1
 #endif
+#ifndef DSS_BOX_ONLY
+#define DSS_BOX_ONLY 0
+#endif
+#if DSS_ALL_SHAPES && DSS_BOX_ONLY
+#error "DSS_BOX_ONLY narrows the lean shape set (DSS_ALL_SHAPES 0)"
+#endif
 #if DSS_ALL_SHAPES
 inline namespace shapes_all {
+#elif DSS_BOX_ONLY
+inline namespace shapes_box {
 #else
 inline namespace shapes_lean {
+#endif
+// "is this body a box": a test of the type word, or (box-only set) a fact of the compilation
+#if DSS_BOX_ONLY
+#define DSS_IS_BOX(type) true
+#else
+#define DSS_IS_BOX(type) ((type) == SHAPE_BOX)
 #endif
 enum ShapeType { SHAPE_BOX = 0, SHAPE_SPHERE = 1, SHAPE_CYLINDER = 2, SHAPE_BOX_ROUNDED = 3, SHAPE_BRICK = 4, SHAPE_BOWL = 5, SHAPE_IGR = 6, SHAPE_GRID = 7 };
 
@@ -336,7 +352,7 @@ template <class T> __host__ __device__ inline void make_shape(Shape<T> &s, int t
     s.grid = nullptr;
     s.gn[0] = s.gn[1] = s.gn[2] = 0;
 #endif
-    if (type == SHAPE_BOX) {
+    if (DSS_IS_BOX(type)) {
         s.scale = t_max(t_max(prm[0], prm[1]), prm[2]) * 1.5 / 2.0;
         for (int i = 0; i < 3; ++i) s.hd[i] = (prm[i] / s.scale) / 2.0;
 #if DSS_ALL_SHAPES
@@ -350,6 +366,7 @@ template <class T> __host__ __device__ inline void make_shape(Shape<T> &s, int t
         for (int i = 0; i < 3; ++i) s.hd[i] = (prm[i] / s.scale) / 2.0;
         s.hd[0] = s.hd[0] - s.hr; s.hd[1] = s.hd[1] - s.hr;
 #endif
+#if !DSS_BOX_ONLY
     } else if (type == SHAPE_CYLINDER) {   // bodies.py:913-921: scale = 1.5 max(rad, height/2), params rad/scale, height/scale
         s.scale = t_max(prm[0], prm[1] / 2.0) * 1.5;
         s.hd[0] = prm[0] / s.scale; s.hd[1] = (prm[1] / s.scale) / 2.0; s.hd[2] = T(0.0);
@@ -364,6 +381,7 @@ template <class T> __host__ __device__ inline void make_shape(Shape<T> &s, int t
     } else {
         s.scale = prm[0] * 1.5;
         s.hd[0] = prm[0] / s.scale; s.hd[1] = T(0.0); s.hd[2] = T(0.0);
+#endif
     }
 }
 
@@ -415,7 +433,7 @@ template <class T> __host__ __device__ inline void sdf_unit(const Shape<T> &s, c
 #if DSS_ALL_SHAPES
     if (s.type == SHAPE_BOX || s.type == SHAPE_BOX_ROUNDED) {
 #else
-    if (s.type == SHAPE_BOX) {
+    if (DSS_IS_BOX(s.type)) {
 #endif
         T q[3], m[3];
         for (int i = 0; i < 3; ++i) q[i] = t_abs(p[i]) - s.hd[i];
@@ -439,6 +457,7 @@ template <class T> __host__ __device__ inline void sdf_unit(const Shape<T> &s, c
             normalize(go, g1);
             normalize(g1, g);  // query_sdfs normalises again (bodies.py:748)
         }
+#if !DSS_BOX_ONLY
     } else if (s.type == SHAPE_CYLINDER) {
         // cylinder_sdf / cylinder_sdf_grad (bodies.py:85-124): a 2-D box SDF in (radial, axial) coordinates
         const T rho = t_sqrt(p[0] * p[0] + p[1] * p[1]);
@@ -553,6 +572,7 @@ template <class T> __host__ __device__ inline void sdf_unit(const Shape<T> &s, c
         const T n = norm3(p);
         phi = n - s.hd[0];
         if (want_grad) { T g1[3]; normalize(p, g1); normalize(g1, g); }
+#endif
     }
 }
 

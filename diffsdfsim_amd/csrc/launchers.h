@@ -7,10 +7,13 @@
 
 namespace dss {
 // narrowphase.hip: contact detection at the current pose (the lean compilation hands over to the full one, narrowphase_all.hip,
-// when DssWorld.shape_rare is set); narrowphase_igr.hip: the query rounds of the pairs with a neural SDF body
+// when DssWorld.shape_rare is set, and to the box-only one, narrowphase_box.hip, when DssWorld.shape_box is);
+// narrowphase_igr.hip: the query rounds of the pairs with a neural SDF body
 int launch_find_contacts(const DssWorld &W, int *nc_out, int *body_out, int *face_out, double *abc_out,
                          double *geom_out, hipStream_t stream);
 int launch_find_contacts_all(const DssWorld &W, int *nc_out, int *body_out, int *face_out, double *abc_out,
+                             double *geom_out, hipStream_t stream);
+int launch_find_contacts_box(const DssWorld &W, int *nc_out, int *body_out, int *face_out, double *abc_out,
                              double *geom_out, hipStream_t stream);
 int launch_igr_rounds(const DssWorld &W, hipStream_t stream);
 // igr_mlp.hip: one evaluation round over a device-side point list / over the value list and the gradient list of a query round

@@ -23,10 +23,17 @@
 // and the hull stage prepared for level-set meshes -- coincident contact points, normal clusters beyond the LDS scratch;
 // only launch_find_contacts_all is exported).  DssWorld.shape_rare picks the variant at launch.  The lean kernel sits at a
 // register-allocation equilibrium: the full variant's extra code costs it 25 %.
+// A third compilation, through narrowphase_box.hip (DSS_BOX_ONLY 1: the lean source with the sphere and cylinder branches
+// of every SDF query taken out by the preprocessor; only launch_find_contacts_box is exported), serves the batches in which
+// every body of every scene is a box (DssWorld.shape_box): the same statements run, so the results are the lean kernel's bit
+// for bit, and the code that never ran no longer costs registers at every merge point.
 #ifndef DSS_ALL_SHAPES
 #define DSS_ALL_SHAPES 0
 #endif
-#if !DSS_ALL_SHAPES
+#ifndef DSS_BOX_ONLY
+#define DSS_BOX_ONLY 0
+#endif
+#if !DSS_ALL_SHAPES && !DSS_BOX_ONLY
 #define DSS_STAMPS np    // phase times of the lean kernel's work items in the diagnostic build (tools/np_phases.py)
 #endif
 
@@ -205,11 +212,13 @@ template <class G> __device__ int narrow_pair(const DssWorld &W, ScratchT<G> &S,
         // the reference also asks for |grad phi| > 1e-12.  The box gradient is a unit vector wherever the query cube
         // is hit (outside: normalised max(q,0); inside/on the surface: the failsafe direction has norm >= 1) and zero
         // outside the cube, so for boxes that test is the cube test and the gradient need not be evaluated.
-        const bool box = Bd.g.shape.type == SHAPE_BOX;
+        const bool box = DSS_IS_BOX(Bd.g.shape.type);
         const bool inside = query_sdf(Bd.g.shape, x, phi, g, !box);
         if (box) return (phi < rad + W.eps) && inside;
+#if !DSS_BOX_ONLY
         const double gn = t_sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
         return (phi < rad + W.eps) && (gn > 1e-12);
+#endif
     };
     auto full_face = [&](int f, double pqr[3][3]) -> int {
         double tri[3][3];
@@ -671,11 +680,16 @@ static inline int np_grid(int B, int nb)
 int launch_find_contacts_all(const DssWorld &W, int *nc_out, int *body_out, int *face_out, double *abc_out,
                              double *geom_out, hipStream_t stream)
 {
+#elif DSS_BOX_ONLY
+int launch_find_contacts_box(const DssWorld &W, int *nc_out, int *body_out, int *face_out, double *abc_out,
+                             double *geom_out, hipStream_t stream)
+{
 #else
 int launch_find_contacts(const DssWorld &W, int *nc_out, int *body_out, int *face_out, double *abc_out,
                          double *geom_out, hipStream_t stream)
 {
     if (W.shape_rare) return launch_find_contacts_all(W, nc_out, body_out, face_out, abc_out, geom_out, stream);
+    if (W.shape_box) return launch_find_contacts_box(W, nc_out, body_out, face_out, abc_out, geom_out, stream);
 #endif
     static_assert(BlockGroup::HCAP <= BlockGroup::BT * MAX_CPT && WaveGroup::HCAP <= WaveGroup::BT * MAX_CPT, "mover registers");
     if (W.max_cand < 1 || W.nb < 1) return DSS_E_UNSUPPORTED;
@@ -699,6 +713,6 @@ int launch_find_contacts(const DssWorld &W, int *nc_out, int *body_out, int *fac
 }
 }  // namespace dss
 
-#if !DSS_ALL_SHAPES
+#if !DSS_ALL_SHAPES && !DSS_BOX_ONLY
 extern "C" int dss_np_slots(int B, int nb) { return dss::np_grid(B, nb) * 4; }
 #endif

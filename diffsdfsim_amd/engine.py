@@ -208,7 +208,11 @@ class BatchEngine:
         # Kernel variant (narrowphase.hip, step_bwd.hip): the lean one knows box / sphere / cylinder and thins contact
         # clusters in LDS; the full one has every primitive and is prepared for level-set meshes (coincident contact
         # points, clusters of thousands of contacts).  Full when a rare primitive or a dense mesh on a free body exists.
+        # A batch in which every body of every scene is a box gets the narrow phase's box-only compilation (the lean
+        # kernel with the sphere and cylinder code taken out: the same results, bit for bit).  All three are properties
+        # of the scene set; spec["full_kernels"] = True / False overrides the choice with full / lean.
         full = spec.get("full_kernels")
+        box_only = full is None and bool((np.asarray(spec["shape_type"]) == abi.SHAPE_BOX).all())
         if full is None:
             full = bool((np.asarray(spec["shape_type"]) > abi.SHAPE_CYLINDER).any())      # (includes neural bodies)
             mid = np.asarray(spec["mesh_id"]).reshape(B, nb)
@@ -217,6 +221,7 @@ class BatchEngine:
                 if not pinned and max(len(spec["meshes"][m][1]) for m in set(mid[:, b].tolist())) > 20000:
                     full = True
         W.shape_rare = int(bool(full))
+        W.shape_box = int(box_only and not full)
         W.max_sub = max_sub
         W.igr_items_cap, W.igr_qcap, W.igr_rounds = self.igr_items_cap, self.igr_qcap, int(spec.get("igr_rounds", 0))
         net_names = ["igr_" + k for k in abi.IGR_NET_POINTERS]

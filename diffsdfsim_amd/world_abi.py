@@ -69,6 +69,7 @@ class DssIgrNet(ctypes.Structure):
 FIELDS = [
     ("B", "i"), ("nb", "i"), ("neq", "i"), ("maxc", "i"), ("fric_dirs", "i"), ("max_cand", "i"), ("max_pc", "i"),
     ("nmesh", "i"), ("strict_no_pen", "i"), ("toc_diff", "i"), ("lcp_max_iter", "i"), ("shape_rare", "i"), ("grad_flags", "i"),
+    ("shape_box", "i"),
     ("eps", "d"), ("tol", "d"), ("dt", "d"),
     ("pose", "pd"), ("vel", "pd"),
     ("mass", "pd"), ("inertia", "pd"), ("restitution", "pd"), ("fric", "pd"), ("fext", "pd"),

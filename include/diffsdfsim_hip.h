@@ -131,8 +131,13 @@ typedef struct DssWorld {
     int nmesh, strict_no_pen, toc_diff /* World3D(time_of_contact_diff=...) */, lcp_max_iter;
     int shape_rare;   /* 0 = lean kernel variants: every shape_type is box / sphere / cylinder and no normal cluster of a
                          body pair exceeds 1024 contacts (analytic meshes); 1 = full variants (all primitives, level-set
-                         meshes).  See narrowphase.hip. */
+                         meshes).  See narrowphase.hip; shape_box below narrows 0 further. */
     int grad_flags;   /* World3D's gradient switches (physics3d/world.py:33-37), reverse sweep only: DSS_GRAD_* */
+    int shape_box;    /* 1 = every shape_type of the batch is DSS_SHAPE_BOX (and shape_rare is 0): the narrow phase runs its
+                         box-only compilation, the lean kernel without the sphere and cylinder code -- the same results bit for
+                         bit.  0 = no such promise.  The field occupies what was alignment padding before `eps`: no other
+                         field moves and the struct's size is unchanged, so DSS_ABI_VERSION stays (a caller that never sets
+                         it leaves it 0 = the lean kernel). */
     double eps, tol, dt;   /* Defaults3D.EPSILON / TOL (utils.py:45-48), world dt */
     /* body state [B][nb][7] / [B][nb][6] */
     double *pose, *vel;

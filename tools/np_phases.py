@@ -13,6 +13,7 @@ if KIND == "sphere":
     E.run(150)
 else:
     spec = scenes.box_stack(B, nbox=7, seed=1)
+    spec["full_kernels"] = False      # the stamps sit in the lean kernel: keep a batch of boxes off the box-only compilation
     E = BatchEngine(spec, maxc=128, max_cand=1024, max_pc=48, strict_no_pen=False, backend=TorchBackend("cuda"))
 np_ = E.nb * (E.nb - 1)
 dbg = torch.zeros(B * np_ * 8, dtype=torch.int64, device="cuda")
