@@ -2,7 +2,7 @@
 // kernel variant (box / sphere / cylinder bodies), restating what torch.autograd does with FWContactHandler._compute_contacts
 // (sdf_physics/physics3d/contacts.py:161-214) and SDF3D.query_sdfs (bodies.py:721-760).
 //
-// The forward-mode version (step_bwd.hip: contact_vjp, Dual<4>) differentiates the same chain five times over, once per
+// The forward-mode version (step_bwd_all.hip: contact_vjp, Dual<4>) differentiates the same chain five times over, once per
 // group of inputs; here the chain is walked forward once in plain doubles and backward once, every primitive handing its
 // output adjoint to its inputs.  The non-smooth pieces follow geom.h's Dual rules, which follow torch's: abs'(0) = 0,
 // clamp passes the gradient on its boundary, max(a, b) routes it to one argument (the first on a tie), torch.max(q, 0)

@@ -22,7 +22,7 @@ int launch_igr_list(const DssIgrNet &N, const double *pts, const int *lat_idx, c
 int launch_igr_pair(const DssIgrNet &N, const double *pts_v, const int *lat_v, const int *n_v, double *sdf_v, const double *pts_g,
                     const int *lat_g, const int *n_g, double *sdf_g, double *grad_g, const double *latents, int lat_stride, int n_cap,
                     hipStream_t stream, int est_v, int est_g);
-// step_bwd_all.hip: first stage of the reverse sweep with every primitive SDF; lcp_contact.hip: dss_lcp_contact_backward for
+// step_bwd_all.hip: first stage of the reverse sweep, full variant (bwd_pre_kernel over step_bwd_pre.h); lcp_contact.hip: dss_lcp_contact_backward for
 // the rows of G that carry gradient (1 normal | 2 friction), multipliers optionally read from tape slot slot[s]
 void launch_bwd_pre_all(const DssWorld &W, const DssAdjoint &A, hipStream_t stream);
 int lcp_contact_backward_rows(const double *Mblk, const double *A, const double *cop, const int *cbody, const int *nc,

@@ -60,6 +60,30 @@ def test_gradients_match_reference_autograd(name, nsteps, copies):
     assert (gp == gp[:1]).all(), "replicated scenes must give identical gradients"
 
 
+@pytest.mark.parametrize("name,nsteps", [("rollout_sphere", 24), ("rollout_boxdrop", 12)])
+def test_full_kernel_variants_agree_with_the_lean_ones(name, nsteps):
+    """The device twin of tests/test_emu_step.py's test of the same name: the same goldens through the full variants of the
+    narrow phase and the contact adjoint (selected with spec['full_kernels'], reached through launch_bwd_pre_all):
+    bit-identical state, gradients equal to rounding."""
+    from diffsdfsim_amd.engine import BatchEngine
+    g = R.load_rollout(name)
+    out = []
+    for full in (False, True):
+        spec = R.spec_from_golden(g)
+        spec["full_kernels"] = full
+        E = BatchEngine(spec, max_sub=64, **R.engine_kwargs(g))
+        assert int(E.W.shape_rare) == int(full)
+        R.rollout_and_sweep(E, nsteps)
+        out.append((E.get("pose").copy(), E.get("vel").copy(), E.get("nsub").copy(), E.be.to_numpy(E.adj["g_prm"]).copy()))
+    for a, b in zip(out[0][:3], out[1][:3]):
+        assert np.array_equal(a, b)
+    # the lean reverse sweep differentiates the contact geometry in reverse mode, the full one in forward mode: the same
+    # derivative to rounding
+    ga, gb = out[0][3], out[1][3]
+    assert np.abs(gb).max() > 0.0
+    assert np.abs(ga - gb).max() < 3e-8 * np.abs(gb).max()      # (rounding differences of 1e-16 grow through 57 sub-steps)
+
+
 def test_pair_that_outgrows_the_wavefront_scratch_matches_reference():
     """A wide flat box on the floor has ~800 contacts before thinning: the wavefront that starts the pair hands it
     to the deferred list, a whole workgroup redoes it.  Same contacts, same trajectory as the reference."""
