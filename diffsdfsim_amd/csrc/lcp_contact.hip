@@ -693,8 +693,8 @@ lcp_contact_forward_kernel(const double *Mblk_, const double *pvec_, const doubl
     // is factored then -- 40 % of the elimination work of the full system.
     bool pinned0 = false;
     if constexpr (N > 12) {
-        bool okl = true;
-        if (lane < nz)
+        bool okl = neq == 6;    // before any read of A: it has six rows only then (neq = 0: A is null)
+        if (okl && lane < nz)
             for (int e = 0; e < 6; ++e) okl = okl && (A[e * nz + lane] == (lane == e ? 1.0 : 0.0));
         pinned0 = neq == 6 && __ballot(!okl) == 0ull;
     }

@@ -36,9 +36,12 @@ def _leaf(x):
     return torch.tensor(x, dtype=torch.double, requires_grad=True)
 
 
-def _scene(floor_phys, movers):
-    """floor_phys = (mass, fric, rest); movers = [(kind, pos6, shape, vel6, (mass, fric, rest), wrench6)], kind in box / sphere /
-    cylinder.  Returns (bodies, joints, leaves) with `leaves` an ordered {name: tensor}."""
+def _scene(floor_phys, movers, joints=(), walls=(), gravity=GRAVITY):
+    """floor_phys = (mass, fric, rest), or None for a scene without floor; movers = [(kind, pos6, shape, vel6, (mass, fric, rest),
+    wrench6)], kind in box / sphere / cylinder; joints = [(constraint class name, body index)] on top of the floor's and the walls'
+    TotalConstraint3D; walls = [(pos6, dims, (mass, fric, rest))]: further pinned boxes, numbered after the floor and before the
+    movers.  Returns (bodies, joints, leaves) with `leaves` an ordered {name: tensor}."""
+    from sdf_physics.physics3d import constraints as C
     from sdf_physics.physics3d.bodies import SDFBox, SDFCylinder, SDFSphere
     from sdf_physics.physics3d.constraints import TotalConstraint3D
     from sdf_physics.physics3d.forces import ExternalForce3D, Gravity3D
@@ -48,9 +51,13 @@ def _scene(floor_phys, movers):
         for k, x in zip(("mass", "fric", "rest"), vals):
             L["%s_%d" % (k, b)] = _leaf(float(x))
         return dict(mass=L["mass_%d" % b], fric_coeff=L["fric_%d" % b], restitution=L["rest_%d" % b], custom_mesh=True, custom_inertia=True)
-    floor = SDFBox([0, -0.5, 0], [4.0, 1.0, 4.0], **phys(0, floor_phys))
-    bodies, shapes = [floor], []
-    for b, (kind, pos, shape, vel, ph, wrench) in enumerate(movers, start=1):
+    bodies, shapes = [], []
+    if floor_phys is not None:
+        bodies.append(SDFBox([0, -0.5, 0], [4.0, 1.0, 4.0], **phys(0, floor_phys)))
+    for pos, dims, ph in walls:
+        bodies.append(SDFBox(list(pos), list(dims), **phys(len(bodies), ph)))
+    pinned = list(bodies)
+    for b, (kind, pos, shape, vel, ph, wrench) in enumerate(movers, start=len(bodies)):
         L["vel_%d" % b] = _leaf(list(vel))
         kw = dict(vel=L["vel_%d" % b], **phys(b, ph))
         if kind == "box":
@@ -65,12 +72,13 @@ def _scene(floor_phys, movers):
         L["pose_%d" % b] = body.p.detach().clone().requires_grad_()
         body.set_p(L["pose_%d" % b])
         L["wrench_%d" % b] = _leaf(list(wrench))
-        body.add_force(Gravity3D(GRAVITY))
+        if gravity:
+            body.add_force(Gravity3D(gravity))
         body.add_force(ExternalForce3D(lambda t, w=L["wrench_%d" % b]: w, multiplier=1.0))
         bodies.append(body)
     for i, s in enumerate(shapes):
         L["shape_%d" % i] = s
-    return bodies, [TotalConstraint3D(floor)], L
+    return bodies, [TotalConstraint3D(b) for b in pinned] + [getattr(C, name)(bodies[b]) for name, b in joints], L
 
 
 def boxdrop():
@@ -116,22 +124,61 @@ def sphere():
                                      [0.02, -0.03, 0.025, 0.8, 0.5, -0.6])])
 
 
+# ---- scenes whose equality rows are not "six rows on body 0" (tests/test_step_constraints_gpu.py) ----
+def rotlocked_box():
+    """The tilted box of boxdrop() under RotConstraint3D (three unit rows on its angular velocity: neq = 9): it keeps its tilt,
+    comes down on one corner through a time-of-contact event and slides on it (friction saturated)."""
+    g = torch.Generator().manual_seed(7)
+    dims = 0.5 + 0.2 * torch.rand(3, generator=g, dtype=torch.double)
+    ang = 0.3 * (torch.rand(3, generator=g, dtype=torch.double) - 0.5)
+    pos = ang.tolist() + [0.0, 0.25 + 0.5 * dims.max().item(), 0.0]
+    return _scene((1.0, 0.55, 0.15), [("box", pos, dims.tolist(), [0.0, 0.0, 0.0, 1.5, -0.5, 0.6], (1.3, 0.3, 0.45),
+                                       [0.05, -0.08, 0.06, 0.3, 0.2, -0.25])], joints=[("RotConstraint3D", 1)])
+
+
+def planar_sphere():
+    """A small sphere under ZConstraint (one unit row on its z velocity: neq = 7), spinning about all three axes against its
+    motion on a smooth floor.  (Radius 0.45 rested on up to seven mesh contacts and the reference's own two runs were 1.7e-3
+    apart; with 0.25 they agree to 1e-12.)"""
+    return _scene((1.0, 0.1, 0.6), [("sphere", [0.1, -0.2, 0.15, 0.0, 0.5, 0.0], 0.25, [0.5, 0.3, 6.0, 0.7, 0.0, 0.0], (1.4, 0.04, 0.4),
+                                     [0.02, -0.03, 0.025, 0.8, 0.5, -0.6])], joints=[("ZConstraint", 1)])
+
+
+def two_pinned():
+    """Floor and a pinned wall box (bodies 0 and 1: neq = 12, n = 18 + 12); a sphere thrown into the corner they form hits
+    both.  The wall hangs 0.06 above the floor (standing on it, the two pinned bodies had 9-15 contacts with each other) and is
+    smooth enough for the sphere to slide along it."""
+    return _scene((1.0, 0.3, 0.3), [("sphere", [0.1, -0.2, 0.15, 0.0, 0.5, 0.0], 0.3, [1.0, 0.5, 3.0, 2.5, -1.0, 0.4], (1.4, 0.2, 0.4),
+                                     [0.02, -0.03, 0.025, 0.6, 0.3, -0.4])],
+                  walls=[([0, 0, 0, 1.0, 0.56, 0.0], [0.5, 1.0, 3.0], (2.0, 0.03, 0.5))])
+
+
+def three_free():
+    """No floor, no joint, no gravity (nb = 3, neq = 0: n = 18 without equality rows): a sphere and a second sphere fly at a
+    slowly tumbling box from two sides."""
+    return _scene(None, [
+        ("sphere", [0.1, -0.2, 0.15, -0.75, 0.05, 0.0], 0.25, [1.0, 2.0, -1.5, 2.0, 0.3, 0.1], (0.9, 0.3, 0.4), [0.02, -0.03, 0.025, 0.2, 0.1, -0.1]),
+        ("box", [0.2, -0.1, 0.15, 0.0, 0.0, 0.0], [0.6, 0.5, 0.7], [0.3, -0.2, 0.4, 0.0, 0.1, 0.0], (1.5, 0.4, 0.3), [0.03, 0.02, -0.04, -0.1, 0.2, 0.15]),
+        ("sphere", [-0.1, 0.3, 0.2, 0.85, -0.05, 0.1], 0.3, [-2.0, 6.0, 5.0, -3.0, 0.2, -0.3], (1.1, 0.03, 0.5), [0.01, -0.02, 0.015, -0.2, 0.1, 0.15])],
+        gravity=0.0)
+
+
 LOSSES = ("", "quatonly_", "velonly_")
 
 
-def losses(bodies, cp, cv, parts):
+def losses(bodies, cp, cv, parts, fixed=(0,)):
     """The general terminal loss and, with `parts`, its quaternion-rows-only and velocity-only pieces."""
-    mv = bodies[1:]
+    mv = [(i, b) for i, b in enumerate(bodies) if i not in fixed]
     tcp, tcv = torch.as_tensor(cp), torch.as_tensor(cv)
-    full = sum((tcp[i] * b.p).sum() + (tcv[i] * b.v).sum() + 0.5 * (b.p ** 2).sum() for i, b in enumerate(mv, start=1))
+    full = sum((tcp[i] * b.p).sum() + (tcv[i] * b.v).sum() + 0.5 * (b.p ** 2).sum() for i, b in mv)
     if not parts:
         return [full]
-    quat = sum((tcp[i, :4] * b.p[:4]).sum() + 0.5 * (b.p[:4] ** 2).sum() for i, b in enumerate(mv, start=1))
-    velo = sum((tcv[i] * b.v).sum() for i, b in enumerate(mv, start=1))
+    quat = sum((tcp[i, :4] * b.p[:4]).sum() + 0.5 * (b.p[:4] ** 2).sum() for i, b in mv)
+    velo = sum((tcv[i] * b.v).sum() for i, b in mv)
     return [full, quat, velo]
 
 
-def rollout(make, nsteps, cp, cv, parts, jitter=0.0, **world_kw):
+def rollout(make, nsteps, cp, cv, parts, jitter=0.0, fixed=(0,), **world_kw):
     bodies, joints, L = make()
     if jitter:
         with torch.no_grad():
@@ -140,7 +187,7 @@ def rollout(make, nsteps, cp, cv, parts, jitter=0.0, **world_kw):
     init = (G.contacts_arrays(w.contacts), contact_record.lookup(w.contacts, MAXC))
     for _ in range(nsteps):
         w.step(fixed_dt=True)
-    ls = losses(bodies, cp, cv, parts)
+    ls = losses(bodies, cp, cv, parts, fixed)
     grads = []
     for l in ls:
         gr = torch.autograd.grad(l, list(L.values()), allow_unused=True, retain_graph=True)
@@ -148,18 +195,34 @@ def rollout(make, nsteps, cp, cv, parts, jitter=0.0, **world_kw):
     return bodies, w, L, init, [float(l) for l in ls], grads
 
 
-def run(name, make, nsteps, seed, toc=True, parts=False, dead=("mass_0",)):
-    bodies, _j, L = make()
+def joint_rows(bodies, joints):
+    """The equality rows as World3D stacks them: every joint's J() in the columns of its body."""
+    nb = len(bodies)
+    Je = np.zeros((sum(j.num_constraints for j in joints), 6 * nb))
+    r = 0
+    for j in joints:
+        J1 = j.J()[0].detach().numpy()
+        b = [k for k, o in enumerate(bodies) if o is j.body1][0]
+        Je[r:r + len(J1), 6 * b:6 * b + 6] = J1
+        r += len(J1)
+    return Je
+
+
+def run(name, make, nsteps, seed, toc=True, parts=False, dead=("mass_0",), fixed=(0,), gravity=GRAVITY, store_Je=False):
+    bodies, joints, L = make()
     nb = len(bodies)
     d = G.describe(bodies)
     rng = np.random.default_rng(seed)
     cp, cv = rng.standard_normal((nb, 7)), rng.standard_normal((nb, 6))
-    cp[0] = 0.0; cv[0] = 0.0      # the pinned floor is not part of the loss
-    bodies, w, L, (init_c, init_s), ls, grads = rollout(make, nsteps, cp, cv, parts, time_of_contact_diff=toc)
+    for b in fixed:
+        cp[b] = 0.0; cv[b] = 0.0      # the pinned bodies are not part of the loss
+    if store_Je:      # (rollout_helpers.spec_from_golden: otherwise six identity rows per body of `fixed`)
+        d["Je"] = joint_rows(bodies, joints)
+    bodies, w, L, (init_c, init_s), ls, grads = rollout(make, nsteps, cp, cv, parts, fixed=fixed, time_of_contact_diff=toc)
     d["dt"], d["eps"], d["tol"], d["fric_dirs"], d["toc_diff"] = w.dt, w.eps, w.tol, w.fric_dirs, int(toc)
-    d["fixed"] = np.array([0], np.int32)
+    d["fixed"] = np.array(list(fixed), np.int32)
     d["strict_no_pen"], d["grad_flags"] = int(w.strict_no_pen), 0
-    d["gravity"], d["loss_cp"], d["loss_cv"] = GRAVITY, cp, cv
+    d["gravity"], d["loss_cp"], d["loss_cv"] = gravity, cp, cv
     d["init_body"], d["init_geom"] = init_c
     d["init_stable"], d["init_lap"] = init_s
     T = len(w.trajectory)
@@ -181,7 +244,7 @@ def run(name, make, nsteps, seed, toc=True, parts=False, dead=("mass_0",)):
     for tag, gr in zip(LOSSES, grads):
         for k, v in gr.items():
             d["grad_%s%s" % (tag, k)] = v
-    _b, wB, _L, (_ic, init_sB), _ls, gradsB = rollout(make, nsteps, cp, cv, parts, jitter=1e-13, time_of_contact_diff=toc)
+    _b, wB, _L, (_ic, init_sB), _ls, gradsB = rollout(make, nsteps, cp, cv, parts, jitter=1e-13, fixed=fixed, time_of_contact_diff=toc)
     stB = G.stable_arrays(wB.trajectory)[0]
     d["init_stableB"] = init_sB[0]
     d["traj_stableB"] = stB if stB.shape == d["traj_stable"].shape else np.full_like(d["traj_stable"], -1)
@@ -209,6 +272,10 @@ CASES = {
     "rollout_general_sphere_on_box": (sphere_on_box, dict(nsteps=12, seed=102)),
     "rollout_general_cylinder": (cylinder, dict(nsteps=10, seed=103)),
     "rollout_general_sphere_notoc": (sphere, dict(nsteps=24, seed=104, toc=False)),
+    "rollout_general_rotlocked_box": (rotlocked_box, dict(nsteps=12, seed=105, store_Je=True)),
+    "rollout_general_planar_sphere": (planar_sphere, dict(nsteps=16, seed=106, store_Je=True)),
+    "rollout_general_two_pinned": (two_pinned, dict(nsteps=16, seed=117, store_Je=True, fixed=(0, 1), dead=("mass_0", "mass_1"))),
+    "rollout_general_three_free": (three_free, dict(nsteps=14, seed=108, store_Je=True, fixed=(), dead=(), gravity=0.0)),
 }
 
 

@@ -16,9 +16,12 @@ def spec_from_golden(g, copies=1, level_set_mesh=None):
     nb = len(g["mass"])
     meshes = [(g["verts_%d" % i], g["faces_%d" % i]) if "verts_%d" % i in g else level_set_mesh(i) for i in range(nb)]
     rep = lambda a: np.repeat(np.asarray(a)[None], copies, axis=0)
-    Je = np.zeros((6 * len(g["fixed"]), 6 * nb))
-    for k, b in enumerate(g["fixed"]):
-        Je[6 * k:6 * k + 6, 6 * b:6 * b + 6] = np.eye(6)   # TotalConstraint3D.J() = I_6 (constraints.py:131-137)
+    if "Je" in g:      # the joints' own rows as the reference stacked them (any constraint class, any body, or none)
+        Je = np.asarray(g["Je"], np.float64).reshape(-1, 6 * nb)
+    else:
+        Je = np.zeros((6 * len(g["fixed"]), 6 * nb))
+        for k, b in enumerate(g["fixed"]):
+            Je[6 * k:6 * k + 6, 6 * b:6 * b + 6] = np.eye(6)   # TotalConstraint3D.J() = I_6 (constraints.py:131-137)
     extra = dict(shape_aux=rep(g["shape_aux"])) if "shape_aux" in g else {}
     if "no_contact" in g:
         extra["no_contact"] = np.asarray(g["no_contact"], np.uint8)

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import equality_rows as EQ
 import structured as S
 from emu import emu
 from helpers import rel
@@ -42,6 +43,26 @@ def test_contact_lcp_forward_backward_vs_dense_oracle(cfg):
         assert rel(dA[s], dAo[0]) < 1e-6 and rel(db[s], dbo[0]) < 1e-6
 
 
+@pytest.mark.parametrize("name", list(EQ.CASES))
+def test_any_block_of_unit_equality_rows_vs_dense_oracle(name):
+    """No rows, partial rows (RotConstraint3D, X/Y/ZConstraint), a pinned body that is not body 0, two pinned bodies: every
+    dispatch of n = 6 nb + neq (equality_rows.CASES), forward and backward, with dA and db."""
+    P = EQ.problem(name)
+    fwd = emu.lcp_contact_forward(P, max_iter=10)
+    bwd = emu.lcp_contact_backward(P, *fwd[:4], EQ.incoming(P))
+    print(name, EQ.check_against_dense_oracle(P, fwd, bwd, need_feasible=name not in EQ.NEVER_FEASIBLE))
+
+
+def test_more_than_64_unknowns_is_refused_by_both_entries():
+    """(nb, neq) = (10, 5): n = 65.  DSS_E_UNSUPPORTED (-3) from the forward and the backward entry, before any launch."""
+    P = EQ.with_unit_rows(S.random_problem(seed=1, B=1, nb=10, maxc=8, fixed_body0=False), [(0, (0, 1, 2, 3, 4))], seed=1)
+    with pytest.raises(AssertionError, match="^-3$"):
+        emu.lcp_contact_forward(P)
+    z = np.zeros
+    with pytest.raises(AssertionError, match="^-3$"):
+        emu.lcp_contact_backward(P, z((1, 60)), z((1, 10, 8)), z((1, 10, 8)), z((1, 5)), z((1, 60)))
+
+
 def test_no_contacts_is_plain_linear_solve():
     P = S.random_problem(seed=5, B=2, nb=2, maxc=4, fd=8)
     P["nc"][:] = 0
@@ -68,14 +89,20 @@ def test_block_tridiagonal_elimination_and_its_fallback_under_the_emulator():
 # (nb, fd, random_problem options): n = 6 nb + neq = 12 (no equality rows), 24, 30 (body 0 pinned), all through the LDS LU; and
 # n = 54 with contacts that do not form a chain, where both forms take the natural register factorisation
 STATE_FORMS = [(2, 8, dict(fixed_body0=False)), (3, 8, {}), (4, 8, {}), (2, 4, dict(fixed_body0=False)), (3, 4, {}),
-               (4, 4, {}), (8, 8, {})]
+               (4, 4, {}), (8, 8, {}),
+               # n = 18 without equality rows, and n = 54 as 7 bodies with bodies 0 and 3 pinned (neq = 12: the general elimination)
+               (3, 8, dict(fixed_body0=False)), (7, 8, dict(fixed_body0=False, joints=[(0, EQ.ALL6), (3, EQ.ALL6)]))]
 
 
 @pytest.mark.parametrize("nb,fd,kw", STATE_FORMS)
 def test_register_and_streamed_state_agree(nb, fd, kw):
     """One forward body, two places for the per-contact IPM state: registers (maxc <= 128) and the streamed workspace (the same
     problem padded to maxc = 136).  The same expressions in the same order between the same barriers: bitwise equal."""
+    kw = dict(kw)
+    joints = kw.pop("joints", None)
     P = S.random_problem(seed=40 + nb + fd, B=2, nb=nb, maxc=128, fd=fd, nc_lo=40, **kw)
+    if joints:
+        P = EQ.with_unit_rows(P, joints, seed=40)
     a = emu.lcp_contact_forward(P, max_iter=20)
     b = emu.lcp_contact_forward(S.pad_contacts(P, 136), max_iter=20)
     for k in (0, 3, 4, 5):      # x, nu, iters, status

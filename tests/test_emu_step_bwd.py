@@ -18,7 +18,12 @@ def test_gradients_match_reference_autograd(name, nsteps):
     R.check_gradients(E, g, tol=1e-3 if name == "rollout_stack2" else 1e-5)
 
 
-@pytest.mark.parametrize("name,nsteps", [("rollout_general_boxdrop", 12), ("rollout_general_sphere_notoc", 24)])
+# (rotlocked_box: RotConstraint3D next to the pinned floor, neq = 9; three_free: no floor, no joint, n = 18 without equality rows)
+TOC_SCENES = ("rollout_general_boxdrop", "rollout_general_rotlocked_box", "rollout_general_three_free")
+
+
+@pytest.mark.parametrize("name,nsteps", [("rollout_general_boxdrop", 12), ("rollout_general_sphere_notoc", 24),
+                                         ("rollout_general_rotlocked_box", 12), ("rollout_general_three_free", 14)])
 def test_every_leaf_matches_reference_autograd(name, nsteps):
     """The assertions of tests/test_step_general_grad_gpu.py where there is no GPU: mass, friction and restitution of every
     body, start pose and velocity, the wrench and the shape, 1e-5 relative per leaf against the reference run the build
@@ -29,5 +34,5 @@ def test_every_leaf_matches_reference_autograd(name, nsteps):
     assert (E.get("nsub") == len(g["traj_t"])).all()
     k = len(g["traj_t"]) - 1
     assert np.abs(E.get("pose")[0] - g["traj_p"][k]).max() < 1e-8 and np.abs(E.get("vel")[0] - g["traj_v"][k]).max() < 1e-8
-    assert bool((E.get("tp_flags") & 1).any()) == (name == "rollout_general_boxdrop"), "time-of-contact events: with toc_diff only"
+    assert bool((E.get("tp_flags") & 1).any()) == (name in TOC_SCENES), "time-of-contact events: with toc_diff only"
     R.check_general(E, g)

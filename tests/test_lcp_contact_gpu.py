@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import equality_rows as EQ
 import structured as S
 from helpers import rel
 
@@ -55,7 +56,9 @@ def test_block_tridiagonal_elimination_and_its_fallback_agree_with_the_dense_ora
 # (nb, fd, random_problem options) as in tests/test_emu_lcp_contact.py: n = 12, 24, 30 through the LDS LU, n = 54 with contacts that do
 # not form a chain (both forms: the natural register factorisation)
 STATE_FORMS = [(2, 8, dict(fixed_body0=False)), (3, 8, {}), (4, 8, {}), (2, 4, dict(fixed_body0=False)), (3, 4, {}),
-               (4, 4, {}), (8, 8, {})]
+               (4, 4, {}), (8, 8, {}),
+               # n = 18 without equality rows, and n = 54 as 7 bodies with bodies 0 and 3 pinned (neq = 12: the general elimination)
+               (3, 8, dict(fixed_body0=False)), (7, 8, dict(fixed_body0=False, joints=[(0, EQ.ALL6), (3, EQ.ALL6)]))]
 
 
 @pytest.mark.parametrize("nb,fd,kw", STATE_FORMS)
@@ -63,7 +66,11 @@ def test_register_and_streamed_state_agree(nb, fd, kw):
     """The forward kernel with the per-contact IPM state in registers (maxc = 128) and streamed through the workspace (the same problem
     padded to maxc = 136).  The emulator has them bitwise equal; on the device a value that goes through memory may meet an FMA that
     the register form does not, so: the same iteration counts and status, results within 1e-12."""
+    kw = dict(kw)
+    joints = kw.pop("joints", None)
     P = S.random_problem(seed=40 + nb + fd, B=2, nb=nb, maxc=128, fd=fd, nc_lo=40, **kw)
+    if joints:
+        P = EQ.with_unit_rows(P, joints, seed=40)
     a = [t.cpu().numpy() for t in run(P, max_iter=20)[1]]
     b = [t.cpu().numpy() for t in run(S.pad_contacts(P, 136), max_iter=20)[1]]
     assert np.array_equal(a[4], b[4]) and np.array_equal(a[5], b[5])
@@ -102,6 +109,38 @@ def test_forward_backward_vs_dense_oracle(cfg):
         wM, wp, wcop = S.contract_dense_grads(P, s, dQ[0], dpo[0], dG[0], dh[0], dF[0])
         assert rel(dM[s], wM) < 1e-6 and rel(dp[s], wp) < 1e-6 and rel(dcop[s], wcop) < 1e-6
         assert rel(dA[s], dAo[0]) < 1e-6 and rel(db[s], dbo[0]) < 1e-6
+
+
+@pytest.mark.parametrize("name", list(EQ.CASES))
+def test_any_block_of_unit_equality_rows_vs_dense_oracle(name):
+    """No rows, partial rows (RotConstraint3D, X/Y/ZConstraint), a pinned body that is not body 0, two pinned bodies: every
+    dispatch of n = 6 nb + neq (equality_rows.CASES), forward and backward, with dA and db.  Worst errors measured on the
+    MI355X: DESIGN.md section 2."""
+    from diffsdfsim_amd.lcp.contact import lcp_contact_backward
+    P = EQ.problem(name)
+    d, fwd = run(P)
+    x, lam, slack, nu = fwd[:4]
+    dl = torch.tensor(EQ.incoming(P), device="cuda")
+    bwd = lcp_contact_backward(d["Mblk"], d["A"], d["cop"], d["cbody"], d["nc"], P["fd"], x, lam, slack, nu, dl, want_dA=True)
+    torch.cuda.synchronize()
+    B, nz = P["Mblk"].shape[0], 6 * P["nb"]
+    bwd = [v.cpu().numpy() if v is not None else np.zeros(s) for v, s in zip(bwd, (0, 0, 0, (B, 0, nz), (B, 0)))]      # no rows: no dA, db
+    worst = EQ.check_against_dense_oracle(P, [v.cpu().numpy() for v in fwd], bwd,
+                                          need_feasible=name not in EQ.NEVER_FEASIBLE)
+    print("%s: %s" % (name, ", ".join("%s %.1e" % kv for kv in worst.items())))
+
+
+def test_more_than_64_unknowns_is_refused_by_both_entries():
+    """(nb, neq) = (10, 5): n = 65.  DSS_E_UNSUPPORTED (-3) from the forward and the backward entry, before any launch."""
+    from diffsdfsim_amd._lib import HipLibraryError
+    from diffsdfsim_amd.lcp.contact import lcp_contact_backward
+    P = EQ.with_unit_rows(S.random_problem(seed=1, B=1, nb=10, maxc=8, fixed_body0=False), [(0, (0, 1, 2, 3, 4))], seed=1)
+    d = dev(P)
+    with pytest.raises(HipLibraryError, match="dss_lcp_contact_forward failed with code -3$"):
+        run(P)
+    z = lambda *s: torch.zeros(*s, dtype=torch.float64, device="cuda")
+    with pytest.raises(HipLibraryError, match="dss_lcp_contact_backward failed with code -3$"):
+        lcp_contact_backward(d["Mblk"], d["A"], d["cop"], d["cbody"], d["nc"], 8, z(1, 60), z(1, 10, 8), z(1, 10, 8), z(1, 5), z(1, 60), want_dA=True)
 
 
 def test_against_dense_hip_kernel():
