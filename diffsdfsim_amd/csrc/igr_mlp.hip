@@ -321,7 +321,8 @@ template <int MODE> struct Variants<NetBobSpot, MODE> {
         // workgroups per CU, so that one's softplus epilogue hides under another's MFMAs; measured 41.9 / 58.1 TFLOP/s without /
         // with tangents against 39.7 / 57.8 for 4 row groups); small ones (a Frank-Wolfe round moves a few points per item): one row group per
         // workgroup, a quarter of the latency of a pass and four times as many workgroups to spread over the chip.
-        // All variants give bit-identical results (a point's row never mixes with its tile-mates').
+        // All variants give bit-identical results (a point's row never mixes with its tile-mates'): held on the device, for both
+        // networks and every mode, by tests/test_igr_variants_gpu.py::test_variant_equals_chunks_of_1024_bit_for_bit.
         const int n = Q.n_dev ? (est < 0 ? n_cap : est) : n_cap;
         if (n >= 16 * 1024) launch<NetBobSpot, 4, 2, MODE>(Q, N, n_cap, est, stream);
         else if (n >= 2 * 1024) launch<NetBobSpot, 2, 2, MODE>(Q, N, n_cap, est, stream);
@@ -359,7 +360,7 @@ inline int net_kind(const DssIgrNet &N)
     if (w == NetShapenet::H && l == NetShapenet::L) return NET_SHAPENET;
     return -1;
 }
-inline bool net_ok(const DssIgrNet *N) { return N && N->W0 && N->b0 && N->Wp && N->bh && N->W8 && N->b8 && net_kind(*N) >= 0; }
+inline bool net_ok(const DssIgrNet *N) { return N && N->W0 && N->b0 && N->Wp && N->bh && N->W8 && N->b8; }
 
 }  // namespace
 
@@ -423,7 +424,9 @@ int dss_igr_query_latent_grad(const double *pts, const double *latent, const dou
 int dss_igr_query_list(const DssIgrNet *net, const double *pts, const int *lat_idx, const double *latents, int lat_stride,
                        const int *n_dev, int n_cap, int mode, double *sdf, double *grad, void *stream)
 {
-    if (!net_ok(net) || !pts || !latents || !sdf || n_cap <= 0 || lat_stride < (net->latent ? net->latent : 2)) return DSS_E_BADARG;
+    if (!net_ok(net) || !pts || !latents || !sdf || n_cap <= 0) return DSS_E_BADARG;
+    if (net_kind(*net) < 0) return DSS_E_UNSUPPORTED;   // a shape no kernel is built for (its .latent says nothing about lat_stride)
+    if (lat_stride < (net->latent ? net->latent : NetBobSpot::L)) return DSS_E_BADARG;
     if (mode != MODE_VALUE && mode != MODE_XYZ && mode != MODE_LATENT) return DSS_E_BADARG;
     if (mode != MODE_VALUE && !grad) return DSS_E_BADARG;
     return dss::launch_igr_list(*net, pts, lat_idx, latents, lat_stride, n_dev, n_cap, mode, sdf, grad, (hipStream_t)stream, -1);
