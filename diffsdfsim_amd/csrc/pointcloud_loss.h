@@ -1,0 +1,30 @@
+// pointcloud_loss.h -- C ABI of the point-cloud loss (csrc/pointcloud_loss.hip), exported by libdiffsdfsim_hip.so beside the
+// functions of include/diffsdfsim_hip.h, whose conventions it shares (device pointers into caller-owned memory, double =
+// binary64 row-major, int = int32, stream = hipStream_t as void*, DSS_E_* return codes).  Bound by world_abi.OPTIONAL_PROTOTYPES;
+// diffsdfsim_amd/pointcloud.py raises if the library does not export it.
+#pragma once
+#include <stddef.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Point-cloud loss: replaces match_pointcloud (experiments/trajectory_fitting/optim_pointcloud.py:166-201) for nseg
+ * (scene, observed frame) segments in one call, value and Jacobian together.  Segment s has its own pose [7] (quaternion
+ * wxyz + position), shape_type and prm [4] (three shape parameters + the corner radius, a constant of the body) and owns the
+ * world-frame points pts[seg_off[s] : seg_off[s + 1]] (seg_off [nseg + 1] on the device; at most max_seg_len points of a
+ * segment are read).  With p = R(q)^T (x - pos), R normalised by 2 / (q.q) like Body3D.M, and phi = the body's SDF at p:
+ *   out[s] = sum over the points with all(|p| <= scale) of  phi^2, 1, d phi^2 / d pose[7], d phi^2 / d prm[3]      [12]
+ * (points outside the query cube add nothing, as `sdf_values[overlap_mask == False] = 0` there; the derivative w.r.t. the raw
+ * quaternion components holds for a non-unit q).  No atomics: two calls on the same input return the same bits.
+ * Analytic primitives only: a segment of DSS_SHAPE_IGR / DSS_SHAPE_GRID gives DSS_E_UNSUPPORTED and leaves `out` untouched.
+ * The status depends on shape_type, so this call (unlike the others) copies those nseg ints to the host and waits for the
+ * stream before it enqueues its two kernels. */
+size_t dss_pointcloud_loss_workspace_bytes(int nseg, int max_seg_len);
+int dss_pointcloud_loss(int nseg, int max_seg_len, const int *seg_off, const double *pts, const double *pose,
+                        const int *shape_type, const double *prm, double *out, void *workspace, size_t workspace_bytes,
+                        void *stream);
+
+#ifdef __cplusplus
+}
+#endif

@@ -21,6 +21,11 @@ inertia fitting of primitives  (experiments/inertia_fitting/optim_primitives.py)
     primitive_spin_world(kind, dims)              the same scene for an SDFBox / SDFSphere / SDFCylinder per row of dimensions (:95-115)
     fit_inertia_primitive(kind, ...)              the loop of :160-240 (Adam, dimensions clamped to [0.5, 2])
 
+trajectory fitting to point clouds  (experiments/trajectory_fitting/optim_pointcloud.py)
+    pointcloud_observations(world_target, cam)    the target body's camera-facing mesh vertices per frame (no renderer, no occlusion)
+    pointcloud_frame_loss / pointcloud_trajectory_loss   match_pointcloud (:166-201) over observed frames: one dss_pointcloud_loss call
+    fit_pointcloud(shape='sphere'|'cube', ...)    first-frame fit, then trajectory fit, of the half size and the start pose (:356-668)
+
 system identification  (experiments/system_identification/optim_sysid.py)
     push_world(latents, packed, force, mass, fric, ...)   the floor and a neural-SDF body pushed along it (:104-131), per scene its own
                                                   push, mass and friction coefficient (torch tensors that may require grad)
@@ -31,6 +36,7 @@ system identification  (experiments/system_identification/optim_sysid.py)
     python -m diffsdfsim_amd.experiments inertia --scenes 8 --iters 10
     python -m diffsdfsim_amd.experiments primitives --kind box --scenes 8 --iters 50
     python -m diffsdfsim_amd.experiments sysid --goal mass --scenes 8 --iters 20
+    python -m diffsdfsim_amd.experiments pointcloud --shape sphere --scenes 8 --iters 20
 """
 import argparse
 import math
@@ -127,10 +133,15 @@ def chamfer(a, b):
 
 # ---- trajectory fitting: a sphere thrown at a wall (optim_sphere.py) --------------------------------------------------------
 def bounce_world(radii, use_toc_diff=True, use_friction=True, use_wall=True, use_floor=True, use_gravity=True,
-                 sphere_pos=(0.0, 5.0, 0.0), sphere_vel=(5.0, 0.0, 0.0), run_time=1.5, dt=Defaults3D.DT, device=None):
+                 sphere_pos=(0.0, 5.0, 0.0), sphere_vel=(5.0, 0.0, 0.0), run_time=1.5, dt=Defaults3D.DT, device=None,
+                 shape="sphere", corner_r=0.2, init_pose=None, res=128):
     """optim_sphere.py:77-111 for one scene per radius: floor 20 x 1 x 20, wall [5,5,0] 1 x 10 x 10 (both pinned, no contact
     with each other), a sphere of the scene's radius at (0,5,0) thrown with (5,0,0); restitution 0.5, friction 0.25 (0 without).
-    Analytic meshes and inertias (the reference's custom_mesh / custom_inertia); shape and inertia are functions of `radii`."""
+    Analytic meshes and inertias (the reference's custom_mesh / custom_inertia); shape and inertia are functions of `radii`.
+    shape='cube' (optim_pointcloud.py:152-155): an SDFBoxRounded of dims 2 rad (1,1,1) and corner radius `corner_r` in the
+    sphere's place, with its level-set mesh (marching cubes at `res`) and that mesh's inertia, both functions of `radii`.
+    init_pose [B,7] (quaternion wxyz + position; a tensor that may require grad): the thrown body's start pose, in place of
+    the identity rotation at `sphere_pos`; the world's `pose` is then connected to it."""
     rad = np.asarray(radii.detach().cpu() if torch.is_tensor(radii) else radii, np.float64).reshape(-1)
     B = len(rad)
     fixed = [n for n, on in (("floor", use_floor), ("wall", use_wall)) if on]
@@ -155,13 +166,18 @@ def bounce_world(radii, use_toc_diff=True, use_friction=True, use_wall=True, use
     if len(fixed) == 2:
         nocon[0, 1] = nocon[1, 0] = 1
     spec["no_contact"] = nocon
-    uv, uf = meshes.icosphere(4)
     s_ = nb - 1
+    if shape == "cube":
+        return _bounce_world_cube(spec, radii, rad, s_, mu, corner_r, init_pose, sphere_pos, sphere_vel, use_gravity, use_toc_diff,
+                                  run_time, dt, res, device)
+    uv, uf = meshes.icosphere(4)
     for s in range(B):
         spec["mesh_id"][s, s_] = scenes._add_mesh(spec, cache, ("sphere", float(rad[s])), lambda r=float(rad[s]): (uv * r, uf, uv.copy()))
     spec["shape_type"][:, s_] = abi.SHAPE_SPHERE
     spec["shape_prm"][:, s_, 0] = rad
     spec["pose"][:, s_, 4:] = sphere_pos
+    if init_pose is not None:
+        spec["pose"][:, s_] = init_pose.detach().cpu().numpy()
     spec["vel"][:, s_, 3:] = sphere_vel
     spec["inertia"][:, s_] = 0.4 * rad[:, None, None] ** 2 * np.eye(3)
     spec["fric"][:, s_] = mu
@@ -177,7 +193,64 @@ def bounce_world(radii, use_toc_diff=True, use_friction=True, use_wall=True, use
         ball = (0.4 * r * r)[:, None, None].to(inertia) * torch.eye(3, dtype=torch.float64)      # 2/5 m r^2 (bodies.py:993-994)
         params = dict(shape_prm=prm, inertia=torch.cat([inertia[:, :s_], ball[:, None]], 1))
     steps = int(math.ceil(run_time / dt)) + 2
-    return BatchWorld3D(spec, params=params, dt=dt, time_of_contact_diff=use_toc_diff, max_substeps=8 * steps + 64, device=device)
+    w = BatchWorld3D(spec, params=params, dt=dt, time_of_contact_diff=use_toc_diff, max_substeps=8 * steps + 64, device=device)
+    if init_pose is not None:
+        _connect_start_pose(w, s_, init_pose)
+    w.body_meshes = [(uv * float(x), uf) for x in rad]      # the thrown body's mesh per scene (pointcloud_observations)
+    return w
+
+
+def _connect_start_pose(w, body, init_pose):
+    """The world's state tensor with `body`'s row taken from init_pose [B,7] (values already in the engine): the first step's
+    adjoint of the pose then reaches init_pose."""
+    w.pose = torch.cat([w.pose[:, :body], init_pose.to(w.pose)[:, None], w.pose[:, body + 1:]], 1)
+
+
+def _bounce_world_cube(spec, radii, rad, s_, mu, corner_r, init_pose, pos, vel, use_gravity, use_toc_diff, run_time, dt, res, device):
+    """bounce_world's scene with the rounded cube of optim_pointcloud.py:152-155: level-set mesh and mesh inertia per scene,
+    differentiable w.r.t. the half side `radii` as bounce_world_latent's body is w.r.t. its latent code."""
+    B, nb = spec["pose"].shape[:2]
+    r_t = radii.to(torch.float64).reshape(-1).cpu() if torch.is_tensor(radii) else torch.tensor(rad)
+    spec["shape_aux"] = np.zeros((B, nb))
+    spec["shape_aux"][:, s_] = corner_r
+    spec["shape_type"][:, s_] = abi.SHAPE_BOX_ROUNDED
+    spec["shape_prm"][:, s_] = 2.0 * rad[:, None]
+    one = torch.tensor(1.0, dtype=torch.float64)
+    vts, Is, body_meshes = [torch.as_tensor(m[0], dtype=torch.float64) for m in spec["meshes"]], [], []
+    for s in range(B):
+        scale = 1.5 * r_t[s]                                              # max(dims) * 1.5 / 2
+        unit = torch.stack([2.0 * r_t[s], 2.0 * r_t[s], 2.0 * r_t[s], torch.tensor(corner_r, dtype=torch.float64)]) / scale
+        v, f = meshsdf.primitive_mesh(abi.SHAPE_BOX_ROUNDED, unit, res=res)
+        v = v * scale.to(v.device)
+        Is.append(mass_properties.mesh_inertia_diff(v, f, one).cpu())
+        spec["meshes"].append((v.detach().cpu().numpy(), f.cpu().numpy())); spec["mesh_vgrad"].append(np.zeros((v.shape[0], 3)))
+        spec["mesh_id"][s, s_] = len(spec["meshes"]) - 1
+        body_meshes.append(spec["meshes"][-1])
+        vts.append(v)
+    spec["pose"][:, s_, 4:] = pos
+    if init_pose is not None:
+        spec["pose"][:, s_] = init_pose.detach().cpu().numpy()
+    spec["vel"][:, s_, 3:] = vel
+    spec["inertia"][:, s_] = torch.stack(Is).detach().numpy()
+    spec["fric"][:, s_] = mu
+    spec["restitution"][:, s_] = Defaults3D.RESTITUTION
+    if use_gravity:
+        spec["fext"][:, s_, 4] = -10.0
+    params = {}
+    if r_t.requires_grad:
+        prm = torch.tensor(spec["shape_prm"], dtype=torch.float64)
+        inertia = torch.tensor(spec["inertia"], dtype=torch.float64)
+        dev = vts[-1].device
+        params = dict(shape_prm=torch.cat([prm[:, :s_], (2.0 * r_t)[:, None, None].expand(B, 1, 3)], 1),
+                      inertia=torch.cat([inertia[:, :s_], torch.stack(Is)[:, None]], 1), verts=torch.cat([v.to(dev) for v in vts]))
+    steps = int(math.ceil(run_time / dt)) + 2
+    # (a flat face of the level-set mesh landing on the floor makes every one of its ~10^4 vertices a contact candidate)
+    w = BatchWorld3D(spec, params=params, dt=dt, time_of_contact_diff=use_toc_diff, max_substeps=8 * steps + 64, device=device,
+                     maxc=256, max_cand=32768, max_pc=128)
+    if init_pose is not None:
+        _connect_start_pose(w, s_, init_pose)
+    w.body_meshes = body_meshes
+    return w
 
 
 def fit_sphere_radius(target_radii, start_radii, run_time=1.5, max_iter=100, lr=0.1, conv_thresh=1e-5, min_dim=0.4, max_dim=2.0,
@@ -224,6 +297,182 @@ def radius_error_table(results):
         err = np.abs(r["radius"] - r["target"])
         rows.append("%-22s min %.1e  mean %.4f  max %.4f   (%d scenes)" % (name, err.min(), err.mean(), err.max(), len(err)))
     return "\n".join(rows)
+
+
+# ---- trajectory fitting to point clouds (trajectory_fitting/optim_pointcloud.py) -------------------------------------------
+def camera_pose():
+    """The experiment's camera (optim_pointcloud.py:408-415): 20 back along z, then Ry(pi/4) Rx(-pi/4); 4 x 4, camera to world."""
+    g = t = math.pi / 4
+    Ry = np.array([[math.cos(g), 0, math.sin(g), 0], [0, 1, 0, 0], [-math.sin(g), 0, math.cos(g), 0], [0, 0, 0, 1.0]])
+    Rx = np.array([[1, 0, 0, 0], [0, math.cos(-t), -math.sin(-t), 0], [0, math.sin(-t), math.cos(-t), 0], [0, 0, 0, 1.0]])
+    T = np.eye(4); T[2, 3] = 20.0
+    return Ry @ Rx @ T
+
+
+def _vertex_normals(v, f):
+    n = np.zeros_like(v)
+    fn = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    for k in range(3):
+        np.add.at(n, f[:, k], fn)
+    return n / np.maximum(np.linalg.norm(n, axis=1, keepdims=True), 1e-300)
+
+
+def pointcloud_observations(world_target, cam_pose, noise=0.0, every=1, run_time=1.5, seed=0, body=-1):
+    """What the experiment's depth camera records of the target body (Recorder3D with record_points, optim_pointcloud.py:420-423),
+    without a renderer: `world_target` (a fresh bounce_world with `body_meshes`) is stepped to run_time and, for the start
+    state and after every `every`-th outer step, the body's mesh vertices that face the camera -- normal . (vertex - camera) < 0,
+    exact for the two convex shapes of the experiment -- are taken as the observed points of that frame, in the world frame.
+    OCCLUSION BY THE WALL AND THE FLOOR IS IGNORED AND NOTHING IS RASTERISED: every camera-facing vertex is seen.
+    noise: the reference's depth_noise_factor -- a point at depth d along the optical axis is moved along its ray by
+    N(0, (noise d^2)^2).  Returns dict(pts [N,3] on the world's device, seg_off [nseg+1], time [nseg], scene [nseg]); segment 0..B-1
+    are the start states (time -dt: no trajectory entry carries that stamp), the others are stamped like run_world_fixed_dt's
+    entries, with the time at the start of the (last sub-step of the) outer step whose end state they show."""
+    B = world_target.B
+    cam = np.asarray(cam_pose, np.float64)
+    c, axis = cam[:3, 3], -cam[:3, 2]                       # OpenGL convention: the camera looks along its -z
+    rng = np.random.default_rng(seed)
+    world_target.record_substeps = True
+    normals = [_vertex_normals(np.asarray(v, np.float64), np.asarray(f)) for v, f in world_target.body_meshes]
+    pts, off, times, scene = [], [0], [], []
+
+    def frame(pose, stamp, mask):
+        for s in range(B):
+            if not mask[s]:
+                continue
+            v = np.asarray(world_target.body_meshes[s][0], np.float64)
+            r_, i, j, k = pose[s, :4]
+            ts = 2.0 / (pose[s, :4] ** 2).sum()
+            R = np.array([[1 - ts * (j * j + k * k), ts * (i * j - k * r_), ts * (i * k + j * r_)], [ts * (i * j + k * r_), 1 - ts * (i * i + k * k), ts * (j * k - i * r_)],
+                          [ts * (i * k - j * r_), ts * (j * k + i * r_), 1 - ts * (i * i + j * j)]])
+            x = v @ R.T + pose[s, 4:]
+            seen = x[((normals[s] @ R.T) * (x - c)).sum(1) < 0]
+            if noise > 0:
+                ray = seen - c
+                d = ray @ axis
+                seen = c + ray * (1.0 + rng.standard_normal(len(seen)) * noise * d)[:, None]      # (d + N(0, noise d^2)) / d
+            pts.append(seen); off.append(off[-1] + len(seen)); times.append(float(stamp[s])); scene.append(s)
+    with torch.no_grad():
+        frame(world_target.pose[:, body].cpu().numpy(), np.full(B, -world_target.dt), np.ones(B, bool))
+        k = 0
+        while True:
+            mask = world_target.t < run_time
+            if not mask.any():
+                break
+            world_target.step(mask=mask, keep_undo=False)
+            k += 1
+            if k % every == 0:
+                frame(world_target.pose[:, body].cpu().numpy(), world_target.substeps["last_t"].cpu().numpy(), mask)
+    return dict(pts=torch.as_tensor(np.concatenate(pts)).to(world_target.device), seg_off=np.asarray(off, np.int64),
+                time=np.asarray(times), scene=np.asarray(scene, np.int64))
+
+
+def _cloud_prm(shape, rad, corner_r):
+    """Shape type and parameter rows [B,4] of the estimate: sphere (rad, 0, 0, 0), cube (2 rad, 2 rad, 2 rad, corner_r)."""
+    z = torch.zeros_like(rad)
+    if shape == "sphere":
+        return abi.SHAPE_SPHERE, torch.stack([rad, z, z, z], 1)
+    return abi.SHAPE_BOX_ROUNDED, torch.stack([2 * rad, 2 * rad, 2 * rad, z + corner_r], 1)
+
+
+def pointcloud_frame_loss(obs, segs, pose, rad, shape, corner_r=0.2, match=None):
+    """sum / max(1, count) per scene of the point-cloud loss over the segments `segs` of `obs`, segment i seen from the pose
+    pose[i] [7] of scene obs['scene'][segs[i]] with half size rad[scene] (optim_pointcloud.py:198-201, 284-285).  -> [B] on the
+    device.  match: the loss of the segments (default pointcloud.match_pointcloud, the HIP kernel)."""
+    from . import pointcloud
+    match = match or pointcloud.match_pointcloud
+    dev = obs["pts"].device
+    B = rad.numel()
+    kind, prm = _cloud_prm(shape, rad.to(dev), corner_r)
+    sc = torch.as_tensor(obs["scene"][segs], device=dev)
+    off = obs["seg_off"]
+    idx = np.concatenate([np.arange(off[i], off[i + 1]) for i in segs]) if len(segs) else np.zeros(0, np.int64)
+    loc = np.concatenate([[0], np.cumsum([off[i + 1] - off[i] for i in segs])]).astype(np.int64)
+    s, n = match(obs["pts"][torch.as_tensor(idx, device=dev)], loc, pose.to(dev), torch.full((len(segs),), kind, dtype=torch.int32), prm[sc])
+    tot = torch.zeros(B, dtype=torch.float64, device=dev).index_add(0, sc, s)
+    cnt = torch.zeros(B, dtype=torch.float64, device=dev).index_add(0, sc, n.to(torch.float64))
+    return tot / cnt.clamp_min(1.0)
+
+
+def pointcloud_trajectory_loss(traj, obs, rad, shape, corner_r=0.2, body=-1, match=None):
+    """trajectory_loss of optim_pointcloud.py:204-290, its point-cloud part: every valid trajectory entry whose stamp is within
+    1e-5 of an observation's time is compared with that observation's points; per scene sum / max(1, count).  -> [B]"""
+    t, ok = traj["t"].cpu().numpy(), traj["valid"].cpu().numpy()
+    segs, ent = [], []
+    for i in range(len(obs["time"])):
+        s = obs["scene"][i]
+        hit = np.nonzero(ok[:, s] & (np.abs(t[:, s] - obs["time"][i]) <= 1e-5))[0]
+        for k in hit:
+            segs.append(i); ent.append((k, s))
+    dev = traj["pose"].device
+    ent = np.asarray(ent, np.int64).reshape(-1, 2)
+    pose = traj["pose"][torch.as_tensor(ent[:, 0], device=dev), torch.as_tensor(ent[:, 1], device=dev), body]
+    return pointcloud_frame_loss(obs, np.asarray(segs, np.int64), pose, rad, shape, corner_r, match)
+
+
+def fit_pointcloud(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_pose=None, start_pose=None, run_time=1.5, max_iter=200,
+                   lr=0.1, optimizer="GD", conv_thresh=1e-5, conv_thresh_shape=1e-3, min_dim=0.5, max_dim=2.5, noise=0.0, every=1,
+                   detach_2nd_bounce=True, fit_first_frame=True, fit_trajectory=True, optimize_pose=True, corner_r=0.2, seed=0,
+                   log=None, **scene):
+    """optim_pointcloud.py:356-668 for B scenes at once, shape 'sphere' (SDFSphere of radius rad) or 'cube' (SDFBoxRounded of
+    dims 2 rad (1,1,1), r = 0.2).  The target's camera-facing points come from pointcloud_observations; the estimate's half
+    size `rad` [B] and, with optimize_pose, its start pose [B,7] are fitted in two stages with the same variables:
+      first frame   the loss of observation 0 seen from the start pose (:428-522),
+      trajectory    the scene rolled out with run_world_fixed_dt(..., detach_2nd_bounce) and compared at the observed frames
+                    (pointcloud_trajectory_loss; :545-633).
+    GD or Adam; after a step rad is clamped to [min_dim, max_dim] and the quaternion renormalised; a scene whose loss moved by
+    less than conv_thresh and its rad by less than conv_thresh_shape is frozen (the scenes are independent optimisations).
+    Returns dict(rad, pose, target_rad, target_pose, history: {'frame': [...], 'trajectory': [...]})."""
+    T = lambda a: torch.as_tensor(np.asarray(a, np.float64))
+    target_rad = T(target_rad).reshape(-1)
+    B = target_rad.numel()
+    ident = torch.tensor([1.0, 0, 0, 0, 0.0, 5.0, 0.0], dtype=torch.float64).repeat(B, 1)
+    target_pose = ident.clone() if target_pose is None else T(target_pose).reshape(B, 7)
+    with torch.no_grad():
+        obs = pointcloud_observations(bounce_world(target_rad, run_time=run_time, shape=shape, corner_r=corner_r, init_pose=target_pose, **scene),
+                                      camera_pose(), noise=noise, every=every, run_time=run_time, seed=seed)
+    rad = T(start_rad).reshape(-1).clone().requires_grad_()
+    start_pose = target_pose.clone() if start_pose is None else T(start_pose).reshape(B, 7)
+    rot, pos = start_pose[:, :4].clone().requires_grad_(optimize_pose), start_pose[:, 4:].clone().requires_grad_(optimize_pose)
+    var = [rad] + ([rot, pos] if optimize_pose else [])
+    first = np.nonzero(obs["time"] < 0)[0]
+    hist = {}
+    for stage in [n for n, on in (("frame", fit_first_frame), ("trajectory", fit_trajectory)) if on]:
+        opt = torch.optim.Adam(var, lr=lr) if optimizer == "Adam" else torch.optim.SGD(var, lr=lr)
+        done, last, last_rad, h = np.zeros(B, bool), np.full(B, 1e10), np.full(B, 1e10), []
+        for e in range(max_iter):
+            opt.zero_grad()
+            pose0 = torch.cat([rot, pos], 1)
+            if stage == "frame":
+                loss = pointcloud_frame_loss(obs, first, pose0[obs["scene"][first]], rad, shape, corner_r)
+            else:
+                world = bounce_world(rad, run_time=run_time, shape=shape, corner_r=corner_r, init_pose=pose0, **scene)
+                traj = run_world_fixed_dt(world, run_time, detach_2nd_bounce=detach_2nd_bounce)
+                loss = pointcloud_trajectory_loss(traj, obs, rad, shape, corner_r)
+            loss.sum().backward()
+            l, r_now = loss.detach().cpu().numpy(), rad.detach().numpy().copy()
+            done |= (np.abs(last - l) < conv_thresh) & (np.abs(last_rad - r_now) < conv_thresh_shape)
+            h.append(dict(iter=e, loss=l.copy(), rad=r_now, pose=pose0.detach().numpy().copy(), grad_rad=rad.grad.numpy().copy(), done=done.copy()))
+            if log:
+                log("[%s] iter %3d  mean loss %.3e  mean |rad - rad*| %.4f  mean |pos - pos*| %.4f  converged %d / %d" %
+                    (stage, e, float(l.mean()), float(np.abs(r_now - target_rad.numpy()).mean()),
+                     float((pos.detach() - target_pose[:, 4:]).norm(dim=1).mean()), int(done.sum()), B))
+            if done.all():
+                break
+            frozen = torch.as_tensor(done)
+            for v in var:
+                v.grad[frozen] = 0.0
+            keep = [v.detach().clone() for v in var]
+            opt.step()
+            with torch.no_grad():
+                for v, k in zip(var, keep):      # (Adam's momentum would still move a frozen scene)
+                    v[frozen] = k[frozen]
+                rad.clamp_(min_dim, max_dim)
+                if optimize_pose:
+                    rot /= rot.norm(dim=1, keepdim=True)
+            last, last_rad = l, r_now
+        hist[stage] = h
+    return dict(rad=rad.detach().numpy().copy(), pose=torch.cat([rot, pos], 1).detach().numpy().copy(), target_rad=target_rad.numpy(),
+                target_pose=target_pose.numpy(), history=hist, observations=obs)
 
 
 # ---- trajectory fitting in shape space: a neural-SDF body thrown at a wall (trajectory_fitting/optim_shapespace.py) ----------
@@ -558,7 +807,9 @@ def export_trajectory(path, pose, vel, **meta):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="batched experiment drivers (trajectory_fitting/optim_sphere, inertia_fitting/optim_shapespace and optim_primitives, system_identification/optim_sysid)")
-    ap.add_argument("what", choices=["sphere", "shapespace", "inertia", "primitives", "sysid"])
+    ap.add_argument("what", choices=["sphere", "shapespace", "inertia", "primitives", "sysid", "pointcloud"])
+    ap.add_argument("--shape", default="sphere", choices=["sphere", "cube"], help="pointcloud: the fitted body")
+    ap.add_argument("--optimizer", default="GD", choices=["GD", "Adam"])
     ap.add_argument("--kind", default="box", choices=sorted(PRIMITIVES))
     ap.add_argument("--goal", default="mass", choices=["mass", "force", "friction"])
     ap.add_argument("--run-time", type=float, default=1.0)
@@ -580,6 +831,18 @@ def main(argv=None):
         print(radius_error_table(res))
         if a.out:
             np.savez_compressed(a.out, **{k.replace(" ", "_").replace(",", ""): v["radius"] for k, v in res.items()}, target=target, start=start)
+    elif a.what == "pointcloud":
+        # optim_pointcloud.py:365-402: target half size ~ U(0.5, 1.5), start = target + U(0, 1); target pose = identity at
+        # (0,5,0) perturbed by N(0, 0.1) in rotation and position, start pose = target pose perturbed the same way again
+        tgt = 0.5 + r.random(a.scenes); st = tgt + r.random(a.scenes)
+        def perturbed(base):
+            q = base[:, :4] + 0.1 * r.standard_normal((a.scenes, 4))
+            return np.concatenate([q / np.linalg.norm(q, axis=1, keepdims=True), base[:, 4:] + 0.1 * r.standard_normal((a.scenes, 3))], 1)
+        tp = perturbed(np.tile([1.0, 0, 0, 0, 0, 5.0, 0], (a.scenes, 1))); sp = perturbed(tp)
+        res = fit_pointcloud(a.shape, tgt, st, tp, sp, run_time=a.run_time, max_iter=a.iters, optimizer=a.optimizer, noise=1e-4, log=print)
+        print("pointcloud %s: mean |rad - rad*| %.4f -> %.4f, mean |pos - pos*| %.4f -> %.4f, %d scenes" %
+              (a.shape, np.abs(st - tgt).mean(), np.abs(res["rad"] - tgt).mean(), np.linalg.norm(sp[:, 4:] - tp[:, 4:], axis=1).mean(),
+               np.linalg.norm(res["pose"][:, 4:] - tp[:, 4:], axis=1).mean(), a.scenes))
     elif a.what == "shapespace":
         from . import igr
         width, nlat = igr.SHAPES[a.net == "shapenet"]

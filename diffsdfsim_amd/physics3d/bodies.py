@@ -86,6 +86,17 @@ class Body3D:
         prm = torch.cat([self.shape_prm().detach().reshape(-1).to(torch.float64), torch.tensor([self.shape_aux()], dtype=torch.float64)])
         return mass_properties.sdf_query(self.shape_type, prm, pts_loc, return_grads, return_overlapmask)
 
+    def pointcloud_loss(self, pts_world):
+        """`match_pointcloud` (experiments/trajectory_fitting/optim_pointcloud.py:166-201) for this body at its pose `p`:
+        world-frame points [n,3] -> (sum of sdf^2 over the points inside the body's query cube, their number), on the device.
+        Differentiable w.r.t. the pose and the shape parameters (dss_pointcloud_loss returns the Jacobian with the value)."""
+        from .. import pointcloud
+        pts = mass_properties._dev(pts_world)
+        prm = torch.cat([self.shape_prm().reshape(-1).to(torch.float64), torch.tensor([self.shape_aux()], dtype=torch.float64)])
+        s, n = pointcloud.match_pointcloud(pts, [0, pts.shape[0]], self.p.to(torch.float64).to(pts.device)[None],
+                                           torch.tensor([self.shape_type], dtype=torch.int32), prm.to(pts.device)[None])
+        return s[0], n[0]
+
     def shape_aux(self):
         """Constant fourth shape parameter (corner radius of SDFBoxRounded / SDFBrick); 0 for the other bodies."""
         return 0.0

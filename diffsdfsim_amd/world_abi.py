@@ -40,8 +40,10 @@ PROTOTYPES = {
     "dss_contacts2d_forward": ("i", "iippppppdpppp"), "dss_contacts2d_backward": ("i", "iippppppdppppp"),
 }
 # outside the public header, bound where a library exports them: the diagnostic build (csrc/diag_stamps.h,
-# csrc/diag_latency.hip) and the CPU emulator's test hook (tests/emu/lcp_dense_wave.cpp)
+# csrc/diag_latency.hip), the CPU emulator's test hook (tests/emu/lcp_dense_wave.cpp) and the point-cloud loss
+# (csrc/pointcloud_loss.h; every product library exports it, diffsdfsim_amd/pointcloud.py raises where one does not)
 OPTIONAL_PROTOTYPES = {
+    "dss_pointcloud_loss_workspace_bytes": ("z", "ii"), "dss_pointcloud_loss": ("i", "iipppppppzp"),
     "dss_diag_set_lcp_stamps": ("v", "pp"), "dss_diag_set_np_stamps": ("v", "pp"), "dss_diag_latency": ("v", "iiippppp"),
     "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"],
 }
