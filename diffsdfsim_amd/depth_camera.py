@@ -1,0 +1,125 @@
+"""Depth camera on the device: what the experiment's Recorder3D(record_points=True, record_seg=True) records and what
+match_pointcloud (experiments/trajectory_fitting/optim_pointcloud.py:168-187) selects from it, by the kernels of
+csrc/depth_camera.hip (ABI: csrc/depth_camera.h).
+
+    depth, seg = render_depth(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640, 480))
+    pts, seg_off = observed_points(depth, seg, body, cam_pose, fx, fy, cx, cy)
+    pts, seg_off = observe(pose, shape_type, prm, body, cam_pose, fx, fy, cx, cy, noise=...)      # both, in chunks of views
+
+A view is one scene at one frame: `pose` [nview,nbody,7] (quaternion wxyz + position), `shape_type` [nview,nbody] int32, `prm`
+[nview,nbody,4] (three shape parameters + the corner radius), nbody <= 8.  `cam_pose` is the 4 x 4 camera-to-world matrix, OpenGL
+convention; pixel (row, col) looks along the camera-frame direction ((col + 0.5 - cx) / fx, -(row + 0.5 - cy) / fy, -1).
+depth [nview,H,W] float64 is the distance along the optical axis (0: nothing hit within [znear, zfar]), seg [nview,H,W] int32 the
+body hit (-1 none, -2 the trace ran out of iterations).  Boxes, spheres, cylinders and rounded boxes only: any other shape
+raises.  Device tensors only.  Not differentiable: observations are data.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_BODIES = 8
+
+
+def _entry(name):
+    L = _lib.lib()
+    if not hasattr(L, name):      # (declared in csrc/depth_camera.h, outside the public header's table)
+        raise _lib.HipLibraryError("libdiffsdfsim_hip.so does not export %s: rebuild it (python __graft_entry__.py build)" % name)
+    return getattr(L, name)
+
+
+def _camera(cam_pose, dev):
+    cam = torch.as_tensor(np.asarray(cam_pose.detach().cpu() if torch.is_tensor(cam_pose) else cam_pose, np.float64))
+    if tuple(cam.shape) != (4, 4):
+        raise ValueError("cam_pose: the 4 x 4 camera-to-world matrix, got %s" % (tuple(cam.shape),))
+    return cam.to(dev).contiguous()
+
+
+def _intrinsics(fx, fy, cx, cy):
+    fx, fy, cx, cy = float(fx), float(fy), float(cx), float(cy)
+    if not (fx != 0.0 and fy != 0.0 and all(np.isfinite([fx, fy, cx, cy]))):
+        raise ValueError("fx and fy non-zero, cx and cy finite, got %r" % ((fx, fy, cx, cy),))
+    return fx, fy, cx, cy
+
+
+def render_depth(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640, 480), znear=0.1, zfar=100.0):
+    """-> (depth [nview,H,W] float64, seg [nview,H,W] int32) on the device of `pose`; size = (W, H).  See the module's text."""
+    _lib.require_device(pose, prm)
+    if pose.dim() != 3 or pose.shape[2] != 7 or pose.dtype != torch.float64 or prm.dtype != torch.float64 or \
+            tuple(prm.shape) != (pose.shape[0], pose.shape[1], 4):
+        raise ValueError("pose [nview,nbody,7] and prm [nview,nbody,4] as float64, got %s and %s" % (tuple(pose.shape), tuple(prm.shape)))
+    nview, nbody = pose.shape[:2]
+    if nview < 1 or not 1 <= nbody <= MAX_BODIES:
+        raise ValueError("at least one view of 1 to %d bodies, got %d views of %d" % (MAX_BODIES, nview, nbody))
+    W, H = int(size[0]), int(size[1])
+    if W < 1 or H < 1 or nview * W * H > 2 ** 31 - 1:
+        raise ValueError("size = (W, H), positive, nview * W * H < 2^31 (render in chunks of views: observe), got %r for %d views" % (size, nview))
+    if not 0.0 <= znear < zfar:
+        raise ValueError("0 <= znear < zfar, got %r, %r" % (znear, zfar))
+    fx, fy, cx, cy = _intrinsics(fx, fy, cx, cy)
+    dev = pose.device
+    types = torch.as_tensor(shape_type).to(dev, torch.int32).reshape(nview, nbody).contiguous()
+    fn = _entry("dss_depth_render")
+    depth = torch.zeros(nview, H, W, dtype=torch.float64, device=dev)
+    seg = torch.full((nview, H, W), -1, dtype=torch.int32, device=dev)
+    cam, pose, prm = _camera(cam_pose, dev), pose.detach().contiguous(), prm.detach().contiguous()
+    rc = fn(nview, nbody, _lib.ptr(pose), _lib.ptr(types), _lib.ptr(prm), _lib.ptr(cam),
+            fx, fy, cx, cy, W, H, float(znear), float(zfar), _lib.ptr(depth), _lib.ptr(seg), _lib.stream_ptr(dev))
+    if rc == -3:
+        raise _lib.HipLibraryError("dss_depth_render: the renderer takes boxes, spheres, cylinders and rounded boxes "
+                                   "(shape types 0-3), got types %s" % sorted(set(types.reshape(-1).tolist())))
+    _lib.check(rc, "dss_depth_render")
+    return depth, seg
+
+
+def observed_points(depth, seg, body, cam_pose, fx, fy, cx, cy):
+    """The world-frame points of body index `body` in depth / seg [nview,H,W]: its mask eroded by one pixel, pixels of depth 0
+    dropped, back-projected; row-major pixel order per view.  -> (pts [N,3] float64 on the device, seg_off [nview+1] int64 numpy:
+    view v owns pts[seg_off[v]:seg_off[v+1]])."""
+    _lib.require_device(depth, seg)
+    if depth.dim() != 3 or depth.shape != seg.shape or depth.dtype != torch.float64 or seg.dtype != torch.int32:
+        raise ValueError("depth float64 and seg int32, both [nview,H,W], got %s %s and %s %s" %
+                         (tuple(depth.shape), depth.dtype, tuple(seg.shape), seg.dtype))
+    nview, H, W = depth.shape
+    if nview < 1 or H < 1 or W < 1 or nview * H * W > 2 ** 31 - 1:
+        raise ValueError("at least one pixel and nview * H * W < 2^31, got %s" % (tuple(depth.shape),))
+    fx, fy, cx, cy = _intrinsics(fx, fy, cx, cy)
+    dev = depth.device
+    depth, seg = depth.contiguous(), seg.contiguous()
+    count, emit = _entry("dss_depth_points_count"), _entry("dss_depth_points_emit")
+    rows = torch.zeros(nview * H, dtype=torch.int32, device=dev)
+    _lib.check(count(nview, H, W, int(body), _lib.ptr(depth), _lib.ptr(seg), _lib.ptr(rows), _lib.stream_ptr(dev)), "dss_depth_points_count")
+    incl = torch.cumsum(rows, 0, dtype=torch.int64)
+    row_off = (incl - rows).to(torch.int32)
+    seg_off = np.concatenate([[0], incl[H - 1::H].cpu().numpy()]).astype(np.int64)      # (the one read-back: N = seg_off[-1])
+    pts = torch.zeros(int(seg_off[-1]), 3, dtype=torch.float64, device=dev)
+    cam = _camera(cam_pose, dev)
+    _lib.check(emit(nview, H, W, int(body), _lib.ptr(depth), _lib.ptr(seg), _lib.ptr(row_off), _lib.ptr(cam), fx, fy, cx, cy,
+                    _lib.ptr(pts), _lib.stream_ptr(dev)), "dss_depth_points_emit")
+    return pts, seg_off
+
+
+def views_per_chunk(size, max_bytes=256 << 20):
+    """How many views `observe` renders at a time: 12 bytes (depth and segment) per pixel within max_bytes, at least one."""
+    return max(1, int(max_bytes) // (12 * int(size[0]) * int(size[1])))
+
+
+def observe(pose, shape_type, prm, body, cam_pose, fx, fy, cx, cy, size=(640, 480), znear=0.1, zfar=100.0, noise=0.0, seed=0,
+            max_bytes=256 << 20):
+    """render_depth and observed_points over all views, at most `max_bytes` of depth and segment images at a time (a 640 x 480
+    view is 3.7 MB).  noise: the reference's depth_noise_factor, applied between the two kernels as Recorder3D.get_pointcloud
+    does, depth += randn * noise * depth^2 (a pixel of depth 0 stays 0), from a generator seeded with `seed` on the device.
+    -> (pts [N,3], seg_off [nview+1]) as observed_points returns them."""
+    nview = pose.shape[0]
+    per = views_per_chunk(size, max_bytes)
+    gen = torch.Generator(device=pose.device)
+    gen.manual_seed(int(seed))
+    types = torch.as_tensor(shape_type).to(pose.device, torch.int32).reshape(nview, -1)
+    pts, off = [], [np.zeros(1, np.int64)]
+    for v0 in range(0, nview, per):
+        depth, seg = render_depth(pose[v0:v0 + per], types[v0:v0 + per], prm[v0:v0 + per], cam_pose, fx, fy, cx, cy, size, znear, zfar)
+        if noise > 0:
+            depth += torch.randn(depth.shape, dtype=depth.dtype, device=depth.device, generator=gen) * noise * depth ** 2
+        p, o = observed_points(depth, seg, body, cam_pose, fx, fy, cx, cy)
+        pts.append(p); off.append(o[1:] + off[-1][-1])
+    return torch.cat(pts), np.concatenate(off)

@@ -23,6 +23,8 @@ inertia fitting of primitives  (experiments/inertia_fitting/optim_primitives.py)
 
 trajectory fitting to point clouds  (experiments/trajectory_fitting/optim_pointcloud.py)
     pointcloud_observations(world_target, cam)    the target body's camera-facing mesh vertices per frame (no renderer, no occlusion)
+                                                  or, observe='depth', what a 640 x 480 depth camera sees of it past the wall and
+                                                  the floor (depth_camera.py: ray-cast images, eroded segment, back-projection)
     pointcloud_frame_loss / pointcloud_trajectory_loss   match_pointcloud (:166-201) over observed frames: one dss_pointcloud_loss call
     fit_pointcloud(shape='sphere'|'cube', ...)    first-frame fit, then trajectory fit, of the half size and the start pose (:356-668)
 
@@ -317,7 +319,41 @@ def _vertex_normals(v, f):
     return n / np.maximum(np.linalg.norm(n, axis=1, keepdims=True), 1e-300)
 
 
-def pointcloud_observations(world_target, cam_pose, noise=0.0, every=1, run_time=1.5, seed=0, body=-1):
+CAMERA = dict(fx=515.0, fy=515.0, cx=319.5, cy=239.5, size=(640, 480), znear=0.1, zfar=100.0)      # optim_pointcloud.py:86-89, 407
+
+
+def _depth_observations(world_target, cam_pose, noise, every, run_time, seed, body, max_bytes):
+    """pointcloud_observations(observe='depth'): the same frames and stamps, each seen by the depth camera."""
+    from . import depth_camera
+    B, E = world_target.B, world_target.engine
+    world_target.record_substeps = True
+    poses, times, scene = [], [], []
+
+    def frame(pose, stamp, mask):
+        idx = np.nonzero(mask)[0]
+        poses.append(pose[torch.as_tensor(idx, device=pose.device)])
+        times.extend(float(stamp[s]) for s in idx); scene.extend(int(s) for s in idx)
+    with torch.no_grad():
+        frame(world_target.pose.detach(), np.full(B, -world_target.dt), np.ones(B, bool))
+        k = 0
+        while True:
+            mask = world_target.t < run_time
+            if not mask.any():
+                break
+            world_target.step(mask=mask, keep_undo=False)
+            k += 1
+            if k % every == 0:
+                frame(world_target.pose.detach(), world_target.substeps["last_t"].cpu().numpy(), mask)
+        sc = torch.as_tensor(np.asarray(scene, np.int64), device=world_target.device)
+        aux = E.arr["shape_aux"] if "shape_aux" in E.arr else torch.zeros_like(E.arr["shape_prm"][..., 0])
+        prm = torch.cat([E.arr["shape_prm"], aux[..., None]], 2)[sc]
+        pts, off = depth_camera.observe(torch.cat(poses), E.arr["shape_type"][sc], prm, body % world_target.nb, cam_pose, noise=noise,
+                                        seed=seed, max_bytes=max_bytes, **CAMERA)
+    return dict(pts=pts, seg_off=off, time=np.asarray(times), scene=np.asarray(scene, np.int64))
+
+
+def pointcloud_observations(world_target, cam_pose, noise=0.0, every=1, run_time=1.5, seed=0, body=-1, observe="vertices",
+                            max_bytes=256 << 20):
     """What the experiment's depth camera records of the target body (Recorder3D with record_points, optim_pointcloud.py:420-423),
     without a renderer: `world_target` (a fresh bounce_world with `body_meshes`) is stepped to run_time and, for the start
     state and after every `every`-th outer step, the body's mesh vertices that face the camera -- normal . (vertex - camera) < 0,
@@ -326,7 +362,15 @@ def pointcloud_observations(world_target, cam_pose, noise=0.0, every=1, run_time
     noise: the reference's depth_noise_factor -- a point at depth d along the optical axis is moved along its ray by
     N(0, (noise d^2)^2).  Returns dict(pts [N,3] on the world's device, seg_off [nseg+1], time [nseg], scene [nseg]); segment 0..B-1
     are the start states (time -dt: no trajectory entry carries that stamp), the others are stamped like run_world_fixed_dt's
-    entries, with the time at the start of the (last sub-step of the) outer step whose end state they show."""
+    entries, with the time at the start of the (last sub-step of the) outer step whose end state they show.
+    observe='depth': the frames are instead rendered by the experiment's depth camera (CAMERA: 640 x 480, fx = fy = 515) with ALL
+    the world's bodies, so the wall and the floor hide what they hide; the body's segment is eroded by one pixel and back-projected
+    as match_pointcloud does (depth_camera.observe, at most max_bytes of images at a time; noise: depth += N(0, (noise depth^2)^2) per
+    pixel, from a device generator seeded with `seed`).  Same dict, same stamps.  Boxes, spheres, cylinders and rounded boxes only."""
+    if observe == "depth":
+        return _depth_observations(world_target, cam_pose, noise, every, run_time, seed, body, max_bytes)
+    if observe != "vertices":
+        raise ValueError("observe: 'vertices' or 'depth', got %r" % (observe,))
     B = world_target.B
     cam = np.asarray(cam_pose, np.float64)
     c, axis = cam[:3, 3], -cam[:3, 2]                       # OpenGL convention: the camera looks along its -z
@@ -412,9 +456,10 @@ def pointcloud_trajectory_loss(traj, obs, rad, shape, corner_r=0.2, body=-1, mat
 def fit_pointcloud(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_pose=None, start_pose=None, run_time=1.5, max_iter=200,
                    lr=0.1, optimizer="GD", conv_thresh=1e-5, conv_thresh_shape=1e-3, min_dim=0.5, max_dim=2.5, noise=0.0, every=1,
                    detach_2nd_bounce=True, fit_first_frame=True, fit_trajectory=True, optimize_pose=True, corner_r=0.2, seed=0,
-                   log=None, **scene):
+                   log=None, observe="vertices", **scene):
     """optim_pointcloud.py:356-668 for B scenes at once, shape 'sphere' (SDFSphere of radius rad) or 'cube' (SDFBoxRounded of
-    dims 2 rad (1,1,1), r = 0.2).  The target's camera-facing points come from pointcloud_observations; the estimate's half
+    dims 2 rad (1,1,1), r = 0.2).  The target's points come from pointcloud_observations (observe: 'vertices', its camera-facing mesh
+    vertices, or 'depth', what the depth camera sees of it past the wall and the floor); the estimate's half
     size `rad` [B] and, with optimize_pose, its start pose [B,7] are fitted in two stages with the same variables:
       first frame   the loss of observation 0 seen from the start pose (:428-522),
       trajectory    the scene rolled out with run_world_fixed_dt(..., detach_2nd_bounce) and compared at the observed frames
@@ -429,7 +474,7 @@ def fit_pointcloud(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_p
     target_pose = ident.clone() if target_pose is None else T(target_pose).reshape(B, 7)
     with torch.no_grad():
         obs = pointcloud_observations(bounce_world(target_rad, run_time=run_time, shape=shape, corner_r=corner_r, init_pose=target_pose, **scene),
-                                      camera_pose(), noise=noise, every=every, run_time=run_time, seed=seed)
+                                      camera_pose(), noise=noise, every=every, run_time=run_time, seed=seed, observe=observe)
     rad = T(start_rad).reshape(-1).clone().requires_grad_()
     start_pose = target_pose.clone() if start_pose is None else T(start_pose).reshape(B, 7)
     rot, pos = start_pose[:, :4].clone().requires_grad_(optimize_pose), start_pose[:, 4:].clone().requires_grad_(optimize_pose)
@@ -810,6 +855,8 @@ def main(argv=None):
     ap.add_argument("what", choices=["sphere", "shapespace", "inertia", "primitives", "sysid", "pointcloud"])
     ap.add_argument("--shape", default="sphere", choices=["sphere", "cube"], help="pointcloud: the fitted body")
     ap.add_argument("--optimizer", default="GD", choices=["GD", "Adam"])
+    ap.add_argument("--observe", default="vertices", choices=["vertices", "depth"],
+                    help="pointcloud: the target's mesh vertices that face the camera, or what the depth camera sees of it")
     ap.add_argument("--kind", default="box", choices=sorted(PRIMITIVES))
     ap.add_argument("--goal", default="mass", choices=["mass", "force", "friction"])
     ap.add_argument("--run-time", type=float, default=1.0)
@@ -839,7 +886,8 @@ def main(argv=None):
             q = base[:, :4] + 0.1 * r.standard_normal((a.scenes, 4))
             return np.concatenate([q / np.linalg.norm(q, axis=1, keepdims=True), base[:, 4:] + 0.1 * r.standard_normal((a.scenes, 3))], 1)
         tp = perturbed(np.tile([1.0, 0, 0, 0, 0, 5.0, 0], (a.scenes, 1))); sp = perturbed(tp)
-        res = fit_pointcloud(a.shape, tgt, st, tp, sp, run_time=a.run_time, max_iter=a.iters, optimizer=a.optimizer, noise=1e-4, log=print)
+        res = fit_pointcloud(a.shape, tgt, st, tp, sp, run_time=a.run_time, max_iter=a.iters, optimizer=a.optimizer, noise=1e-4, log=print,
+                             observe=a.observe)
         print("pointcloud %s: mean |rad - rad*| %.4f -> %.4f, mean |pos - pos*| %.4f -> %.4f, %d scenes" %
               (a.shape, np.abs(st - tgt).mean(), np.abs(res["rad"] - tgt).mean(), np.linalg.norm(sp[:, 4:] - tp[:, 4:], axis=1).mean(),
                np.linalg.norm(res["pose"][:, 4:] - tp[:, 4:], axis=1).mean(), a.scenes))

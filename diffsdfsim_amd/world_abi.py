@@ -44,6 +44,9 @@ PROTOTYPES = {
 # (csrc/pointcloud_loss.h; every product library exports it, diffsdfsim_amd/pointcloud.py raises where one does not)
 OPTIONAL_PROTOTYPES = {
     "dss_pointcloud_loss_workspace_bytes": ("z", "ii"), "dss_pointcloud_loss": ("i", "iipppppppzp"),
+    # the depth camera (csrc/depth_camera.h; exported by every product library, diffsdfsim_amd/depth_camera.py raises where not)
+    "dss_depth_render": ("i", "iippppddddiiddppp"), "dss_depth_points_count": ("i", "iiiipppp"),
+    "dss_depth_points_emit": ("i", "iiiippppddddpp"),
     "dss_diag_set_lcp_stamps": ("v", "pp"), "dss_diag_set_np_stamps": ("v", "pp"), "dss_diag_latency": ("v", "iiippppp"),
     "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"],
 }
