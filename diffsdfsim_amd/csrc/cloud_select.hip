@@ -1,0 +1,179 @@
+// cloud_select.hip -- the front of the recorded point-cloud fit (experiments/trajectory_fitting/optim_pointcloud_real.py): from
+// label images and organised clouds to the flat pts / seg_off segments dss_pointcloud_loss reads, and the per-frame statistics
+// the script initialises from (bounding-box diameter and centroid of the labelled points, :326-331, :499).  ABI and
+// conventions: cloud_select.h.
+//
+//   dss_cloud_select_count   a wavefront per image row, 64 columns at a time: ballot of the selected pixels, popcount
+//   dss_cloud_select_emit    the same walk; a selected pixel's slot is the row's offset + the popcount of the lanes below it
+//   dss_cloud_stats          256-thread workgroups, one per (segment, chunk of 2 048 points), segment-major flat grid; each
+//                            lane keeps sum / min / max of x, y, z in registers; wavefront butterflies, a fixed tree over the
+//                            four wavefronts in LDS, one partial [10] per workgroup; a second kernel combines a segment's
+//                            partials in index order
+//
+// Memory-bound (4 B read per pixel and 24 B more per labelled pixel, 24 B per point); no atomics, so every output is a
+// function of the input alone.
+#include "../../include/diffsdfsim_hip.h"
+#include "cloud_select.h"
+#include "wave_utils.h"
+
+namespace {
+using namespace dss;
+
+constexpr int CS_THREADS = 256, CS_CHUNK = 2048, CS_OUT = 10, CS_RED = 9;      // CS_RED: the reduced values (count is hi - lo)
+
+__device__ __forceinline__ bool cs_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }      // (false for a NaN)
+
+// is pixel (row r, column c) of the frame at pixel index `base` a point of `label`
+__device__ __forceinline__ bool cs_selected(const double *__restrict__ pcs, const int *__restrict__ segs, size_t base, int W, int r, int c,
+                                            int label)
+{
+    if (c >= W) return false;
+    const size_t i = base + (size_t)r * W + c;
+    if (segs[i] != label) return false;
+    return cs_finite(pcs[3 * i]) && cs_finite(pcs[3 * i + 1]) && cs_finite(pcs[3 * i + 2]);
+}
+
+__global__ void __launch_bounds__(CS_THREADS) cloud_select_count_kernel(int nrow, int H, int W, int label, const double *__restrict__ pcs,
+                                                                       const int *__restrict__ segs, int *__restrict__ rows)
+{
+    const int g = blockIdx.x * (CS_THREADS / WAVE) + threadIdx.x / WAVE, lane = lane_id();
+    if (g >= nrow) return;      // (the whole wavefront)
+    const int frame = g / H, r = g - frame * H;
+    const size_t base = (size_t)frame * H * W;
+    int n = 0;
+    for (int c0 = 0; c0 < W; c0 += WAVE) n += __popcll(__ballot(cs_selected(pcs, segs, base, W, r, c0 + lane, label)));
+    if (lane == 0) rows[g] = n;
+}
+
+__global__ void __launch_bounds__(CS_THREADS) cloud_select_emit_kernel(int nrow, int H, int W, int label, const double *__restrict__ pcs,
+                                                                      const int *__restrict__ segs, const int *__restrict__ row_off,
+                                                                      double *__restrict__ pts)
+{
+    const int g = blockIdx.x * (CS_THREADS / WAVE) + threadIdx.x / WAVE, lane = lane_id();
+    if (g >= nrow) return;
+    const int frame = g / H, r = g - frame * H;
+    const size_t base = (size_t)frame * H * W;
+    int at = row_off[g];
+    for (int c0 = 0; c0 < W; c0 += WAVE) {
+        const int c = c0 + lane;
+        const bool sel = cs_selected(pcs, segs, base, W, r, c, label);
+        const unsigned long long mask = __ballot(sel);
+        if (sel) {
+            const double *in = pcs + 3 * (base + (size_t)r * W + c);
+            double *out = pts + 3 * (size_t)(at + __popcll(mask & ((1ull << lane) - 1ull)));
+#pragma unroll
+            for (int i = 0; i < 3; ++i) out[i] = in[i];
+        }
+        at += __popcll(mask);
+    }
+}
+
+__global__ void __launch_bounds__(CS_THREADS) cloud_stats_kernel(int max_seg_len, int chunks, const int *__restrict__ seg_off,
+                                                                const double *__restrict__ pts, double *__restrict__ partial)
+{
+    __shared__ double red[CS_THREADS / WAVE][CS_RED];
+    const int s = blockIdx.x / chunks, chunk = blockIdx.x - s * chunks, tid = threadIdx.x;
+    const int first = seg_off[s];
+    int len = seg_off[s + 1] - first;
+    if (len > max_seg_len) len = max_seg_len;      // the workspace was sized for max_seg_len
+    const int lo = chunk * CS_CHUNK;
+    if (lo >= len) return;                          // (the whole workgroup: nothing of this segment in the chunk)
+    const int hi = lo + CS_CHUNK < len ? lo + CS_CHUNK : len;
+    const double inf = __builtin_huge_val();
+    double sum[3] = {0.0, 0.0, 0.0}, mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
+    const double *P = pts + 3 * (size_t)first;
+    for (int i = lo + tid; i < hi; i += CS_THREADS) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double v = P[3 * (size_t)i + k];
+            sum[k] += v;
+            mn[k] = fmin(mn[k], v);
+            mx[k] = fmax(mx[k], v);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double a = wave_sum(sum[k]), b = wave_min(mn[k]), c = wave_max(mx[k]);
+        if (lane_id() == 0) { red[tid / WAVE][k] = a; red[tid / WAVE][3 + k] = b; red[tid / WAVE][6 + k] = c; }
+    }
+    __syncthreads();
+    double *out = partial + (size_t)blockIdx.x * CS_OUT;
+    if (tid == 0) out[0] = (double)(hi - lo);
+    if (tid < 3) out[1 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+    else if (tid < 6) out[1 + tid] = fmin(fmin(red[0][tid], red[1][tid]), fmin(red[2][tid], red[3][tid]));
+    else if (tid < 9) out[1 + tid] = fmax(fmax(red[0][tid], red[1][tid]), fmax(red[2][tid], red[3][tid]));
+}
+
+// out[s][k] = the segment's partials combined in index order (count 0, sums 0, min +inf, max -inf for an empty segment)
+__global__ void __launch_bounds__(CS_THREADS) cloud_stats_combine_kernel(int nseg, int max_seg_len, int chunks, const int *__restrict__ seg_off,
+                                                                        const double *__restrict__ partial, double *__restrict__ out)
+{
+    const int t = blockIdx.x * CS_THREADS + threadIdx.x;
+    if (t >= nseg * CS_OUT) return;
+    const int s = t / CS_OUT, k = t - s * CS_OUT;
+    int len = seg_off[s + 1] - seg_off[s];
+    if (len > max_seg_len) len = max_seg_len;
+    const int nch = len > 0 ? (len + CS_CHUNK - 1) / CS_CHUNK : 0;
+    const double inf = __builtin_huge_val();
+    double acc = k < 4 ? 0.0 : (k < 7 ? inf : -inf);
+    for (int c = 0; c < nch; ++c) {
+        const double v = partial[((size_t)s * chunks + c) * CS_OUT + k];
+        acc = k < 4 ? acc + v : (k < 7 ? fmin(acc, v) : fmax(acc, v));
+    }
+    out[t] = acc;
+}
+
+bool cs_images_ok(int nframe, int H, int W) { return (long long)nframe * H * W <= 0x7fffffffLL; }
+int cs_chunks(int max_seg_len) { return (max_seg_len + CS_CHUNK - 1) / CS_CHUNK; }
+
+}  // namespace
+
+extern "C" {
+
+int dss_cloud_select_count(int nframe, int H, int W, int label, const double *pcs, const int *segs, int *rows, void *stream)
+{
+    if (nframe <= 0 || H <= 0 || W <= 0 || !pcs || !segs || !rows) return DSS_E_BADARG;
+    if (!cs_images_ok(nframe, H, W)) return DSS_E_UNSUPPORTED;
+    const int nrow = nframe * H, per = CS_THREADS / WAVE;
+    hipLaunchKernelGGL(cloud_select_count_kernel, dim3((nrow + per - 1) / per), dim3(CS_THREADS), 0, (hipStream_t)stream, nrow, H, W, label,
+                       pcs, segs, rows);
+    return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
+}
+
+int dss_cloud_select_emit(int nframe, int H, int W, int label, const double *pcs, const int *segs, const int *row_off, double *pts,
+                          void *stream)
+{
+    // (pts may be NULL: no pixel selected, nothing is written)
+    if (nframe <= 0 || H <= 0 || W <= 0 || !pcs || !segs || !row_off) return DSS_E_BADARG;
+    if (!cs_images_ok(nframe, H, W)) return DSS_E_UNSUPPORTED;
+    const int nrow = nframe * H, per = CS_THREADS / WAVE;
+    hipLaunchKernelGGL(cloud_select_emit_kernel, dim3((nrow + per - 1) / per), dim3(CS_THREADS), 0, (hipStream_t)stream, nrow, H, W, label,
+                       pcs, segs, row_off, pts);
+    return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
+}
+
+size_t dss_cloud_stats_workspace_bytes(int nseg, int max_seg_len)
+{
+    if (nseg <= 0 || max_seg_len <= 0) return 0;
+    return (size_t)nseg * cs_chunks(max_seg_len) * CS_OUT * sizeof(double);
+}
+
+int dss_cloud_stats(int nseg, int max_seg_len, const int *seg_off, const double *pts, double *out, void *workspace, size_t workspace_bytes,
+                    void *stream)
+{
+    if (nseg <= 0 || max_seg_len < 0 || !seg_off || !out || (max_seg_len > 0 && !pts)) return DSS_E_BADARG;
+    if ((long long)nseg * (cs_chunks(max_seg_len) > 0 ? cs_chunks(max_seg_len) : 1) > 0x7fffffffLL / CS_OUT)
+        return DSS_E_UNSUPPORTED;      // grid.x and the int indices nseg * chunks * CS_OUT, nseg * CS_OUT
+    const size_t need = dss_cloud_stats_workspace_bytes(nseg, max_seg_len);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return DSS_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int chunks = cs_chunks(max_seg_len);
+    if (chunks > 0)
+        hipLaunchKernelGGL(cloud_stats_kernel, dim3(chunks * nseg), dim3(CS_THREADS), 0, st, max_seg_len, chunks, seg_off, pts,
+                           (double *)workspace);
+    hipLaunchKernelGGL(cloud_stats_combine_kernel, dim3((nseg * CS_OUT + CS_THREADS - 1) / CS_THREADS), dim3(CS_THREADS), 0, st, nseg,
+                       max_seg_len, chunks, seg_off, (const double *)workspace, out);
+    return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
+}
+
+}  // extern "C"

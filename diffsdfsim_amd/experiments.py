@@ -28,6 +28,15 @@ trajectory fitting to point clouds  (experiments/trajectory_fitting/optim_pointc
     pointcloud_frame_loss / pointcloud_trajectory_loss   match_pointcloud (:166-201) over observed frames: one dss_pointcloud_loss call
     fit_pointcloud(shape='sphere'|'cube', ...)    first-frame fit, then trajectory fit, of the half size and the start pose (:356-668)
 
+trajectory fitting to recorded RGB-D sequences  (experiments/trajectory_fitting/optim_pointcloud_real.py)
+    plane_pose(planes) / plane_world(rad, planes, fric, restitution, pose, vel, g, shape)   the fitted planes as pinned boxes and the
+                                                  thrown ball or rounded cube (`make_world`, :98-148)
+    run_world_frames(world, nframes, detach_2nd_bounce)   one entry per recorded frame (`run_world_fixed_dt`, :199-223)
+    recorded_observations / recorded_trajectory_loss      the labelled points of every frame (recorded.py: csrc/cloud_select.hip) and
+                                                  entry i against frame i (:170-196)
+    fit_recorded(recordings, shape, ...)          first-frame fit, then trajectory fit over rad, start pose, start velocity, friction and
+                                                  restitution (:326-557); synthesize_recording(...) makes recordings with the depth camera
+
 system identification  (experiments/system_identification/optim_sysid.py)
     push_world(latents, packed, force, mass, fric, ...)   the floor and a neural-SDF body pushed along it (:104-131), per scene its own
                                                   push, mass and friction coefficient (torch tensors that may require grad)
@@ -39,6 +48,7 @@ system identification  (experiments/system_identification/optim_sysid.py)
     python -m diffsdfsim_amd.experiments primitives --kind box --scenes 8 --iters 50
     python -m diffsdfsim_amd.experiments sysid --goal mass --scenes 8 --iters 20
     python -m diffsdfsim_amd.experiments pointcloud --shape sphere --scenes 8 --iters 20
+    python -m diffsdfsim_amd.experiments recorded --file real_world_data.pkl [--shape cube]      (or --synthetic)
 """
 import argparse
 import math
@@ -520,6 +530,324 @@ def fit_pointcloud(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_p
                 target_pose=target_pose.numpy(), history=hist, observations=obs)
 
 
+# ---- trajectory fitting to recorded RGB-D sequences (trajectory_fitting/optim_pointcloud_real.py) ----------------------------
+PLANE_DIMS = (1.5, 1.0, 1.5)      # :104
+BALL_MASS = 0.058                 # :135
+
+
+def plane_pose(planes, dims_y=PLANE_DIMS[1]):
+    """Poses [...,7] of the boxes that stand for the fitted planes [...,4] (rows n, d: the plane n . x + d = 0 seen from the
+    origin), optim_pointcloud_real.py:106-118: the rotation by angle = acos(n . e_y / |n|) about -(n x e_y) / |n x e_y| as a
+    quaternion, and the centre -sign(d) n (|d| + dims_y / 2), n as given (not normalised, as there).  Where n is parallel to e_y,
+    |n x e_y| < 1e-12, the reference divides by zero; here the rotation is then the identity (angle 0) or the half turn about x
+    (angle pi)."""
+    pl = torch.as_tensor(np.asarray(planes.detach().cpu() if torch.is_tensor(planes) else planes, np.float64))
+    n, d = pl[..., :3], pl[..., 3]
+    up = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float64).expand_as(n)
+    angle = torch.arccos((n * up).sum(-1) / n.norm(dim=-1))
+    axis = torch.cross(n, up, dim=-1)
+    an = axis.norm(dim=-1, keepdim=True)
+    par = an < 1e-12
+    axis = axis / torch.where(par, torch.ones_like(an), an)
+    half = (0.5 * angle)[..., None]
+    q = torch.cat([torch.cos(half), -axis * torch.sin(half)], -1)
+    flat = torch.where(angle[..., None] < 0.5 * math.pi, torch.tensor([1.0, 0, 0, 0], dtype=torch.float64), torch.tensor([0.0, 1, 0, 0], dtype=torch.float64))
+    q = torch.where(par, flat, q)
+    pos = -torch.sign(d)[..., None] * n * (d.abs() + 0.5 * dims_y)[..., None]
+    return torch.cat([q, pos], -1)
+
+
+def plane_world(rad, planes, fric, restitution, pose, vel, g=10.0, shape="sphere", corner_r=0.2, res=128, max_steps=128, device=None):
+    """`make_world` of optim_pointcloud_real.py:98-148 for B scenes: P boxes of PLANE_DIMS posed by plane_pose(planes [B,P,4]),
+    pinned and mutually no_contact, and the thrown body -- shape 'sphere': an SDFSphere of radius rad and mass 0.058, 'cube': an
+    SDFBoxRounded of dims 2 rad (1,1,1), r = corner_r and mass 1 -- at pose [B,7] with velocity vel [B,6] (angular, linear)
+    under gravity g ([B] or a number) along -y; every body has the scene's fric [B] and restitution [B].
+    strict_no_penetration and the time-of-contact differential are on.  rad, fric, restitution, pose and vel are torch tensors
+    that may require grad.  Analytic meshes and inertias for the boxes and the sphere (the reference's custom_mesh /
+    custom_inertia), the cube's level-set mesh and its inertia as in bounce_world."""
+    T = lambda x: x.to(torch.float64).cpu() if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, np.float64))
+    rad, fric, restitution, pose, vel = T(rad).reshape(-1), T(fric).reshape(-1), T(restitution).reshape(-1), T(pose), T(vel)
+    B = rad.numel()
+    pl = np.asarray(T(planes).detach(), np.float64)
+    pl = np.array(np.broadcast_to(pl, (B,) + pl.shape[-2:]))
+    P, nb = pl.shape[1], pl.shape[1] + 1
+    s_ = P
+    gv = np.broadcast_to(np.asarray(T(g).detach(), np.float64).reshape(-1), (B,))
+    spec, cache = scenes._base(B, nb), {}
+    spec["Je"] = np.zeros((B, 6 * P, 6 * nb))
+    spec["pose"][:, :P] = plane_pose(pl).numpy()
+    nocon = np.zeros((nb, nb), np.uint8)
+    nocon[:P, :P] = 1 - np.eye(P, dtype=np.uint8)
+    spec["no_contact"] = nocon
+
+    def make():
+        v, f, tie = meshes.box_mesh(np.asarray(PLANE_DIMS))
+        return v, f, 0.5 * tie
+    for k in range(P):
+        spec["mesh_id"][:, k] = scenes._add_mesh(spec, cache, ("box",) + PLANE_DIMS, make)
+        spec["shape_prm"][:, k] = PLANE_DIMS
+        spec["inertia"][:, k] = scenes.box_inertia(1.0, np.asarray(PLANE_DIMS))
+        spec["Je"][:, 6 * k:6 * k + 6, 6 * k:6 * k + 6] = np.eye(6)
+    r_np = rad.detach().numpy()
+    one = torch.tensor(1.0, dtype=torch.float64)
+    verts = None
+    if shape == "sphere":
+        mass = BALL_MASS
+        uv, uf = meshes.icosphere(4)
+        for s in range(B):
+            spec["mesh_id"][s, s_] = scenes._add_mesh(spec, cache, ("sphere", float(r_np[s])), lambda r=float(r_np[s]): (uv * r, uf, uv.copy()))
+        spec["shape_type"][:, s_] = abi.SHAPE_SPHERE
+        z = torch.zeros_like(rad)
+        prm_body = torch.stack([rad, z, z], 1)
+        I_body = (0.4 * mass * rad * rad)[:, None, None] * torch.eye(3, dtype=torch.float64)      # 2/5 m r^2 (bodies.py:993-994)
+    elif shape == "cube":
+        mass = 1.0
+        spec["shape_aux"] = np.zeros((B, nb))
+        spec["shape_aux"][:, s_] = corner_r
+        spec["shape_type"][:, s_] = abi.SHAPE_BOX_ROUNDED
+        vts, Is = [torch.as_tensor(m[0], dtype=torch.float64) for m in spec["meshes"]], []
+        for s in range(B):      # (the level-set mesh and its inertia per scene, as _bounce_world_cube builds them)
+            scale = 1.5 * rad[s]
+            unit = torch.stack([2.0 * rad[s], 2.0 * rad[s], 2.0 * rad[s], torch.tensor(corner_r, dtype=torch.float64)]) / scale
+            v, f = meshsdf.primitive_mesh(abi.SHAPE_BOX_ROUNDED, unit, res=res)
+            v = v * scale.to(v.device)
+            Is.append(mass_properties.mesh_inertia_diff(v, f, one).cpu())
+            spec["meshes"].append((v.detach().cpu().numpy(), f.cpu().numpy())); spec["mesh_vgrad"].append(np.zeros((v.shape[0], 3)))
+            spec["mesh_id"][s, s_] = len(spec["meshes"]) - 1
+            vts.append(v)
+        prm_body = (2.0 * rad)[:, None].expand(B, 3)
+        I_body = torch.stack(Is)
+        if rad.requires_grad:
+            verts = torch.cat([v.to(vts[-1].device) for v in vts])
+    else:
+        raise ValueError("shape: 'sphere' or 'cube', got %r" % (shape,))
+    spec["mass"][:, s_] = mass
+    spec["fext"][:, s_, 4] = -gv * mass
+    prm0, I0 = torch.tensor(spec["shape_prm"], dtype=torch.float64), torch.tensor(spec["inertia"], dtype=torch.float64)
+    params = dict(shape_prm=torch.cat([prm0[:, :s_], prm_body[:, None]], 1), inertia=torch.cat([I0[:, :s_], I_body[:, None]], 1),
+                  fric=fric[:, None].expand(B, nb), restitution=restitution[:, None].expand(B, nb))
+    if verts is not None:
+        params["verts"] = verts
+    for k, v in params.items():
+        if k != "verts":
+            spec[k] = v.detach().numpy().copy()
+    spec["pose"][:, s_] = pose.detach().numpy()
+    spec["vel"][:, s_] = vel.detach().numpy()
+    big = dict(maxc=256, max_cand=32768, max_pc=128) if shape == "cube" else {}
+    w = BatchWorld3D(spec, params=params, dt=Defaults3D.DT, time_of_contact_diff=True, strict_no_penetration=True,
+                     max_substeps=8 * int(max_steps) + 64, device=device, **big)
+    _connect_start_pose(w, s_, pose)
+    w.vel = torch.cat([w.vel[:, :s_], vel.to(w.vel)[:, None], w.vel[:, s_ + 1:]], 1)
+    return w
+
+
+def run_world_frames(world, nframes, detach_2nd_bounce=False, body=-1):
+    """`run_world_fixed_dt` of optim_pointcloud_real.py:199-223 per scene: entry 0 is the body's start pose, then one entry per
+    outer step of Defaults3D.DT, nframes - 1 entries in all (the last observed frame has none, as there).  nframes: a number or
+    [B]; a scene whose frames have ended is masked out of the steps.  detach_2nd_bounce: the second step in a row (since the last
+    cut) that ends in contact is undone, its scene's poses and velocities are cut from the graph, the entry before it is
+    replaced by the cut state (the script pops it and appends it again) and the frame is stepped once more.
+    -> dict(pose [K,B,7] with its graph, valid [K,B], repeated: per scene the frames stepped twice)."""
+    B, dev = world.B, world.device
+    T = np.broadcast_to(np.asarray(nframes, np.int64).reshape(-1), (B,))
+    K = max(int(T.max()) - 1, 1)
+    entries = [world.pose[:, body]] + [None] * (K - 1)
+    frame, num_contact, repeated = np.ones(B, np.int64), np.zeros(B, np.int64), [[] for _ in range(B)]
+    while True:
+        mask = frame < T - 1
+        if not mask.any():
+            break
+        had = np.asarray(world.step(mask=mask)) & mask
+        redo = np.zeros(B, bool)
+        if detach_2nd_bounce:
+            num_contact += had
+            redo = had & (num_contact > 1)
+            if redo.any():
+                world.undo_step(redo)
+                world.detach_state(redo)
+                num_contact[redo] = 0
+                for s in np.nonzero(redo)[0]:
+                    repeated[s].append(int(frame[s]))
+        cur = world.pose[:, body]
+        at = frame - redo
+        for k in np.unique(at[mask]):
+            sel = torch.as_tensor(mask & (at == k), device=dev)[:, None]
+            entries[k] = torch.where(sel, cur, entries[k] if entries[k] is not None else torch.zeros_like(cur))
+        frame = frame + (mask & ~redo)
+    pose = torch.stack([e if e is not None else torch.zeros_like(entries[0]) for e in entries])
+    valid = torch.as_tensor(np.arange(K)[:, None] < np.maximum(T - 1, 1)[None, :], device=dev)
+    return dict(pose=pose, valid=valid, repeated=repeated)
+
+
+def recorded_observations(recordings, label=4):
+    """The thrown body's points of B recordings (dicts with pcs [T,H,W,3], segs [T,H,W] on the device: recorded.load_recording,
+    synthesize_recording) as one set of segments, recording after recording, frame after frame (recorded.select_points), with
+    their statistics (recorded.segment_stats).  -> dict(pts, seg_off, scene [nseg], frame [nseg], first [B] (a scene's first
+    segment), nframes [B], stats)."""
+    from . import recorded
+    pts, off, scene, frame, first = [], [np.zeros(1, np.int64)], [], [], []
+    for b, rec in enumerate(recordings):
+        p, o = recorded.select_points(rec["pcs"], rec["segs"], label)
+        first.append(len(scene))
+        pts.append(p); off.append(o[1:] + off[-1][-1])
+        scene.extend([b] * (len(o) - 1)); frame.extend(range(len(o) - 1))
+    pts, off = torch.cat(pts), np.concatenate(off)
+    return dict(pts=pts, seg_off=off, scene=np.asarray(scene, np.int64), frame=np.asarray(frame, np.int64), first=np.asarray(first, np.int64),
+                nframes=np.asarray([r["segs"].shape[0] for r in recordings], np.int64), stats=recorded.segment_stats(pts, off))
+
+
+def recorded_trajectory_loss(traj, obs, rad, shape, corner_r=0.2, match=None):
+    """`trajectory_loss` of optim_pointcloud_real.py:170-196: entry i of a scene's trajectory (run_world_frames) is compared with
+    the points of its frame i; per scene sum / max(1, count).  -> [B]"""
+    ok = traj["valid"].cpu().numpy()
+    ent = np.argwhere(ok & (np.arange(ok.shape[0])[:, None] < obs["nframes"][None, :]))      # (entry, scene)
+    dev = traj["pose"].device
+    pose = traj["pose"][torch.as_tensor(ent[:, 0], device=dev), torch.as_tensor(ent[:, 1], device=dev)]
+    return pointcloud_frame_loss(obs, obs["first"][ent[:, 1]] + ent[:, 0], pose, rad, shape, corner_r, match)
+
+
+def fit_recorded(recordings, shape="sphere", lr=0.1, max_iter=200, optimizer="GD", conv_thresh=1e-7, conv_thresh_shape=1e-5,
+                 detach_2nd_bounce=True, optimize_init_pose=True, fit_first_frame=True, fit_trajectory=True, start_rad=None,
+                 start_pose0=None, start_pose1=None, corner_r=0.2, label=4, log=None, device=None, res=128):
+    """optim_pointcloud_real.py:326-557 for B recordings at once (dicts of pcs, segs, planes [P,4], g; the same number of planes in
+    each).  From the statistics of the labelled points of frames 0 and 1: diam0 = the largest side of frame 0's bounding box,
+    start radius diam0 / 2, start positions = the two centroids pushed diam0 / 2 away from the origin (:326-336); start_rad [B],
+    start_pose0 / start_pose1 [B,7] replace them.
+      first frame   rad, and with optimize_init_pose the poses of frames 0 and 1, on the loss of those two frames (:366-445)
+      trajectory    rad, rot, pos, vel [6] = (0, (pos1 - pos0) / DT + g DT e_y), fric (0.15), restitution (0.7): plane_world,
+                    run_world_frames(detach_2nd_bounce), recorded_trajectory_loss (:468-556)
+    GD or Adam; as in fit_pointcloud a scene whose loss moved by less than conv_thresh and its rad by less than conv_thresh_shape
+    is frozen; after a step the start rotation is renormalised (frame 1's is not, as in the script).
+    -> (first_frame, trajectory): the script's two result dicts, arrays with a leading [B]."""
+    obs = recorded_observations(recordings, label)
+    B, DT = len(recordings), Defaults3D.DT
+    st = {k: v.cpu() for k, v in obs["stats"].items()}
+    f0, f1 = torch.as_tensor(obs["first"]), torch.as_tensor(obs["first"] + 1)
+    if bool((st["count"][f0] < 1).any() or (st["count"][f1] < 1).any()):
+        raise ValueError("a recording shows no point of label %d in its first two frames" % label)
+    diam0 = (st["max"][f0] - st["min"][f0]).max(dim=1).values
+    push = lambda c: c + c / c.norm(dim=1, keepdim=True) * diam0[:, None] / 2
+    T = lambda a: torch.as_tensor(np.asarray(a, np.float64))
+    ident = torch.tensor([1.0, 0, 0, 0], dtype=torch.float64).repeat(B, 1)
+    pose0 = torch.cat([ident, push(st["mean"][f0])], 1) if start_pose0 is None else T(start_pose0).reshape(B, 7)
+    pose1 = torch.cat([ident, push(st["mean"][f1])], 1) if start_pose1 is None else T(start_pose1).reshape(B, 7)
+    start = (diam0 / 2 if start_rad is None else T(start_rad).reshape(B)).clone()
+    rad = start.clone().requires_grad_()
+    leaf = lambda x: x.clone().requires_grad_(optimize_init_pose)
+    rot0, pos0, rot1, pos1 = leaf(pose0[:, :4]), leaf(pose0[:, 4:]), leaf(pose1[:, :4]), leaf(pose1[:, 4:])
+    planes = torch.stack([T(r["planes"].cpu() if torch.is_tensor(r["planes"]) else r["planes"]).reshape(-1, 4) for r in recordings])
+    g = T([float(r["g"]) for r in recordings])
+
+    def descend(stage, var, loss_fn):
+        opt = torch.optim.Adam(var, lr=lr) if optimizer == "Adam" else torch.optim.SGD(var, lr=lr)
+        done, last, last_rad = np.zeros(B, bool), np.full(B, 1e10), np.full(B, 1e10)
+        h = dict(loss_hist=[], rad_hist=[], init_pose_hist=[])
+        for e in range(max_iter):
+            opt.zero_grad()
+            loss = loss_fn()
+            loss.sum().backward()
+            l, r_now = loss.detach().cpu().numpy(), rad.detach().numpy().copy()
+            done |= (np.abs(last - l) < conv_thresh) & (np.abs(last_rad - r_now) < conv_thresh_shape)
+            h["loss_hist"].append(l.copy()); h["rad_hist"].append(r_now); h["init_pose_hist"].append(torch.cat([rot0, pos0], 1).detach().numpy().copy())
+            if log:
+                log("[%s] iter %3d  mean loss %.3e  mean rad %.5f  converged %d / %d" % (stage, e, float(l.mean()), float(r_now.mean()), int(done.sum()), B))
+            if done.all():
+                break
+            frozen = torch.as_tensor(done)
+            for v in var:
+                if v.grad is None:
+                    v.grad = torch.zeros_like(v)
+                v.grad[frozen] = 0.0
+            keep = [v.detach().clone() for v in var]
+            opt.step()
+            with torch.no_grad():
+                for v, k in zip(var, keep):      # (Adam's momentum would still move a frozen scene)
+                    v[frozen] = k[frozen]
+                if rot0.requires_grad:
+                    rot0.div_(rot0.norm(dim=1, keepdim=True))
+            last, last_rad = l, r_now
+        h["final_loss"] = h["loss_hist"][-1]
+        return h
+
+    first_frame = traj_out = None
+    if fit_first_frame:
+        segs = np.concatenate([obs["first"], obs["first"] + 1])
+        h = descend("first frame", [rad] + ([rot0, rot1, pos0, pos1] if optimize_init_pose else []),
+                    lambda: pointcloud_frame_loss(obs, segs, torch.cat([torch.cat([rot0, pos0], 1), torch.cat([rot1, pos1], 1)]), rad, shape, corner_r))
+        first_frame = dict(start_rad=start.numpy().copy(), final_rad=rad.detach().numpy().copy(), final_pose=torch.cat([rot0, pos0], 1).detach().numpy().copy(),
+                           init_pose1=torch.cat([rot1, pos1], 1).detach().numpy().copy(), **h)
+    if fit_trajectory:
+        rot0.requires_grad_(True); pos0.requires_grad_(True)
+        lin = ((pos1 - pos0) / DT).detach() + torch.tensor([0.0, 1.0, 0.0], dtype=torch.float64) * (g * DT)[:, None]
+        vel = torch.cat([torch.zeros(B, 3, dtype=torch.float64), lin], 1).requires_grad_()
+        fric = torch.full((B,), 0.15, dtype=torch.float64, requires_grad=True)
+        rest = torch.full((B,), 0.7, dtype=torch.float64, requires_grad=True)
+
+        def traj_loss():
+            world = plane_world(rad, planes, fric, rest, torch.cat([rot0, pos0], 1), vel, g, shape, corner_r, res, int(obs["nframes"].max()) + 8, device)
+            return recorded_trajectory_loss(run_world_frames(world, obs["nframes"], detach_2nd_bounce), obs, rad, shape, corner_r)
+        h = descend("trajectory", [rad, rot0, pos0, vel, fric, rest], traj_loss)
+        traj_out = dict(start_rad=start.numpy().copy(), final_rad=rad.detach().numpy().copy(), final_pose=torch.cat([rot0, pos0], 1).detach().numpy().copy(),
+                        init_vel=vel.detach().numpy().copy(), friction=fric.detach().numpy().copy(), restitution=rest.detach().numpy().copy(), **h)
+    return first_frame, traj_out
+
+
+def recording_camera(W=640, H=480):
+    """The pinhole camera of synthesize_recording: at the origin of the recording's frame, looking along -z, +y up; 515 pixels of
+    focal length at 640 x 480 (CAMERA), scaled with the width."""
+    f = CAMERA["fx"] * W / 640.0
+    return dict(fx=f, fy=f, cx=(W - 1) / 2.0, cy=(H - 1) / 2.0, size=(W, H), znear=0.05, zfar=100.0)
+
+
+def synthesize_recording(rad=(0.1,), planes=((0.0, 1.0, 0.0, 0.3), (-1.0, 0.0, 0.0, 0.4)), pos=(-0.25, -0.05, -0.6), vel=(1.2, 0.5, 0.0),
+                         fric=0.15, restitution=0.7, g=9.81, nframes=12, size=(80, 60), shape="sphere", noise=0.0, seed=0, device=None):
+    """Recordings without a camera: plane_world with the given truth rolled out for nframes frames, every frame rendered by
+    depth_camera.render_depth from the origin (recording_camera) and every pixel back-projected to the organised cloud, as a
+    depth sensor's driver does.  Labels: the thrown body 4, plane k -> k + 1, nothing hit 0 (its point is NaN, as a sensor
+    reports a pixel without depth).  One recording per entry of `rad`; planes [P,4] or [B,P,4].
+    -> list of dicts(pcs, segs, planes, grav_dir, g, rgbs=None, truth=dict(rad, pose [nframes,7], vel0, fric, restitution))."""
+    from . import depth_camera
+    rad = torch.as_tensor(np.asarray(rad, np.float64)).reshape(-1)
+    B = rad.numel()
+    pl = np.array(np.broadcast_to(np.asarray(planes, np.float64), (B,) + np.asarray(planes).shape[-2:]))
+    P = pl.shape[1]
+    pose0 = torch.tensor([1.0, 0, 0, 0] + list(pos), dtype=torch.float64).repeat(B, 1)
+    vel0 = torch.tensor([0.0, 0, 0] + list(vel), dtype=torch.float64).repeat(B, 1)
+    full = lambda x: torch.full((B,), float(x), dtype=torch.float64)
+    cam = recording_camera(*size)
+    W, H = cam["size"]
+    with torch.no_grad():
+        w = plane_world(rad, pl, full(fric), full(restitution), pose0, vel0, g, shape, max_steps=nframes + 8, device=device)
+        poses = [w.pose]
+        for _ in range(nframes - 1):
+            w.step(keep_undo=False)
+            poses.append(w.pose)
+        poses = torch.stack(poses, 1)                                           # [B,nframes,nb,7]
+        E = w.engine
+        aux = E.arr["shape_aux"] if "shape_aux" in E.arr else torch.zeros_like(E.arr["shape_prm"][..., 0])
+        prm = torch.cat([E.arr["shape_prm"], aux[..., None]], 2)
+        dev = poses.device
+        col = (torch.arange(W, dtype=torch.float64, device=dev) + 0.5 - cam["cx"]) / cam["fx"]
+        row = (torch.arange(H, dtype=torch.float64, device=dev) + 0.5 - cam["cy"]) / cam["fy"]
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        lab = torch.tensor(list(range(1, P + 1)) + [4, 0], dtype=torch.int32, device=dev)      # body index -> label; -1 (nothing) -> 0
+        out = []
+        for b in range(B):
+            depth, seg = depth_camera.render_depth(poses[b], E.arr["shape_type"][b:b + 1].expand(nframes, -1).contiguous(),
+                                                   prm[b:b + 1].expand(nframes, -1, -1).contiguous(), np.eye(4), **cam)
+            if noise > 0:
+                depth = depth + torch.randn(depth.shape, dtype=depth.dtype, device=dev, generator=gen) * noise * depth ** 2
+            hit = seg >= 0
+            d = torch.where(hit, depth, torch.full_like(depth, float("nan")))
+            pcs = torch.stack([col[None, None, :] * d, -row[None, :, None] * d, -d], 3).contiguous()      # the camera frame is the world frame
+            segs = lab[torch.where(hit, seg, torch.full_like(seg, P + 1)).long()].contiguous()
+            out.append(dict(pcs=pcs, segs=segs, planes=torch.as_tensor(pl[b].copy()), grav_dir=torch.tensor([0.0, -float(g), 0.0], dtype=torch.float64),
+                            g=float(g), rgbs=None,
+                            truth=dict(rad=float(rad[b]), pose=poses[b, :, -1].cpu().numpy(), vel0=vel0[b].numpy(), fric=float(fric), restitution=float(restitution))))
+    return out
+
+
 # ---- trajectory fitting in shape space: a neural-SDF body thrown at a wall (trajectory_fitting/optim_shapespace.py) ----------
 def bounce_world_latent(latents, packed, use_toc_diff=True, use_friction=True, use_wall=True, use_floor=True, use_gravity=False,
                         obj_pos=(0.0, 5.0, 0.0), obj_vel=(5.0, 0.0, 0.0), run_time=1.5, dt=Defaults3D.DT, res=128, device=None):
@@ -852,21 +1180,25 @@ def export_trajectory(path, pose, vel, **meta):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="batched experiment drivers (trajectory_fitting/optim_sphere, inertia_fitting/optim_shapespace and optim_primitives, system_identification/optim_sysid)")
-    ap.add_argument("what", choices=["sphere", "shapespace", "inertia", "primitives", "sysid", "pointcloud"])
-    ap.add_argument("--shape", default="sphere", choices=["sphere", "cube"], help="pointcloud: the fitted body")
+    ap.add_argument("what", choices=["sphere", "shapespace", "inertia", "primitives", "sysid", "pointcloud", "recorded"])
+    ap.add_argument("--shape", default="sphere", choices=["sphere", "cube"], help="pointcloud, recorded: the fitted body")
+    ap.add_argument("--file", default=None, help="recorded: the recording (real_world_data.pkl, or an .npz with its keys)")
+    ap.add_argument("--synthetic", action="store_true", help="recorded: fit recordings made by synthesize_recording instead of --file")
     ap.add_argument("--optimizer", default="GD", choices=["GD", "Adam"])
     ap.add_argument("--observe", default="vertices", choices=["vertices", "depth"],
                     help="pointcloud: the target's mesh vertices that face the camera, or what the depth camera sees of it")
     ap.add_argument("--kind", default="box", choices=sorted(PRIMITIVES))
     ap.add_argument("--goal", default="mass", choices=["mass", "force", "friction"])
     ap.add_argument("--run-time", type=float, default=1.0)
-    ap.add_argument("--scenes", type=int, default=64)
+    ap.add_argument("--scenes", type=int, default=None, help="default 64; recorded --synthetic: 2")
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--net", default="bob_spot", choices=["bob_spot", "shapenet"],
                     help="shapespace, sysid, inertia: the network shape (bob_spot: latent 2, 8 x 128; shapenet: latent 4, 8 x 256)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
+    synthetic_default = a.scenes is None
+    a.scenes = 64 if a.scenes is None else a.scenes
     r = np.random.default_rng(a.seed)
     if a.what == "sphere":
         # RESULTS.md:14-47: radius error after fitting, target and start radii ~ U(0.4, 2.0) (optim_sphere.py:214-218)
@@ -891,6 +1223,24 @@ def main(argv=None):
         print("pointcloud %s: mean |rad - rad*| %.4f -> %.4f, mean |pos - pos*| %.4f -> %.4f, %d scenes" %
               (a.shape, np.abs(st - tgt).mean(), np.abs(res["rad"] - tgt).mean(), np.linalg.norm(sp[:, 4:] - tp[:, 4:], axis=1).mean(),
                np.linalg.norm(res["pose"][:, 4:] - tp[:, 4:], axis=1).mean(), a.scenes))
+    elif a.what == "recorded":
+        if a.synthetic:
+            n = 2 if synthetic_default else a.scenes
+            recs = synthesize_recording(rad=0.08 + 0.04 * r.random(n), shape=a.shape, noise=1e-4, seed=a.seed)
+        elif a.file:
+            from . import recorded
+            recs = [recorded.load_recording(a.file)]
+        else:
+            ap.error("recorded: give --file PATH or --synthetic")
+        first, traj = fit_recorded(recs, shape=a.shape, max_iter=a.iters, optimizer=a.optimizer, log=print)
+        print("%-6s %-10s %-10s %-10s %-12s %-12s %-9s %-9s" % ("scene", "start rad", "frame rad", "traj rad", "frame loss", "traj loss", "friction", "restit."))
+        for s in range(len(recs)):
+            print("%-6d %-10.5f %-10.5f %-10.5f %-12.3e %-12.3e %-9.4f %-9.4f" % (s, first["start_rad"][s], first["final_rad"][s], traj["final_rad"][s],
+                                                                          first["final_loss"][s], traj["final_loss"][s], traj["friction"][s], traj["restitution"][s]))
+        if a.synthetic:
+            tr = np.array([rc["truth"]["rad"] for rc in recs])
+            print("recorded %s: |rad - rad*| start mean %.5f -> first frame %.5f -> trajectory %.5f, %d recordings" %
+                  (a.shape, np.abs(first["start_rad"] - tr).mean(), np.abs(first["final_rad"] - tr).mean(), np.abs(traj["final_rad"] - tr).mean(), len(recs)))
     elif a.what == "shapespace":
         from . import igr
         width, nlat = igr.SHAPES[a.net == "shapenet"]

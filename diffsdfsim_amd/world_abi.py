@@ -47,6 +47,9 @@ OPTIONAL_PROTOTYPES = {
     # the depth camera (csrc/depth_camera.h; exported by every product library, diffsdfsim_amd/depth_camera.py raises where not)
     "dss_depth_render": ("i", "iippppddddiiddppp"), "dss_depth_points_count": ("i", "iiiipppp"),
     "dss_depth_points_emit": ("i", "iiiippppddddpp"),
+    # recorded clouds (csrc/cloud_select.h; exported by every product library, diffsdfsim_amd/recorded.py raises where not)
+    "dss_cloud_select_count": ("i", "iiiipppp"), "dss_cloud_select_emit": ("i", "iiiippppp"),
+    "dss_cloud_stats_workspace_bytes": ("z", "ii"), "dss_cloud_stats": ("i", "iippppzp"),
     "dss_diag_set_lcp_stamps": ("v", "pp"), "dss_diag_set_np_stamps": ("v", "pp"), "dss_diag_latency": ("v", "iiippppp"),
     "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"],
 }
