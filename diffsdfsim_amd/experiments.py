@@ -56,6 +56,7 @@ import math
 import numpy as np
 import torch
 
+from . import chamfer as chamfer_hip
 from . import mass_properties, meshes, meshsdf, scenes
 from . import world_abi as abi
 from .physics3d import BatchWorld3D
@@ -141,6 +142,14 @@ def chamfer(a, b):
         to_a = to_a + d.min(dim=1).values.sum()
         to_b = torch.minimum(to_b, d.min(dim=0).values)
     return to_a / a.shape[0] + to_b.mean()
+
+
+def _chamfer_series(verts, target_cloud):
+    """The report's `chamfer_dist` of one iteration, [B] numpy: the fitted bodies' mesh vertices (a list of [N_s,3] arrays or
+    tensors) against the targets', packed once by chamfer.pack; one batched call (csrc/chamfer.hip), one read-back."""
+    with torch.no_grad():
+        a, a_off = chamfer_hip.pack(verts, target_cloud[0].device)
+        return chamfer_hip.chamfer_packed(a, a_off, *target_cloud).cpu().numpy()
 
 
 # ---- trajectory fitting: a sphere thrown at a wall (optim_sphere.py) --------------------------------------------------------
@@ -272,7 +281,9 @@ def fit_sphere_radius(target_radii, start_radii, run_time=1.5, max_iter=100, lr=
     the scenes of the batch are independent optimisations).  Returns dict(radius [B], history)."""
     target_radii = torch.as_tensor(np.asarray(target_radii, np.float64))
     with torch.no_grad():
-        target = run_world_fixed_dt(bounce_world(target_radii, run_time=run_time, **scene), run_time)
+        wt = bounce_world(target_radii, run_time=run_time, **scene)
+        target = run_world_fixed_dt(wt, run_time)
+        tgt_cloud = chamfer_hip.pack([m[0] for m in wt.body_meshes])
     rad = torch.tensor(np.asarray(start_radii, np.float64), requires_grad=True)
     B = rad.numel()
     done = np.zeros(B, bool)
@@ -287,10 +298,11 @@ def fit_sphere_radius(target_radii, start_radii, run_time=1.5, max_iter=100, lr=
         loss.sum().backward()
         l = loss.detach().cpu().numpy()
         done |= np.abs(last - l) < conv_thresh
-        hist.append(dict(iter=e, loss=l.copy(), radius=rad.detach().numpy().copy(), grad=rad.grad.numpy().copy(), done=done.copy()))
+        d = _chamfer_series([m[0] for m in world.body_meshes], tgt_cloud)
+        hist.append(dict(iter=e, loss=l.copy(), radius=rad.detach().numpy().copy(), grad=rad.grad.numpy().copy(), done=done.copy(), chamfer=d))
         if log:
-            log("iter %3d  mean loss %.3e  mean |r - r*| %.4f  converged %d / %d" %
-                (e, float(l.mean()), float((rad.detach() - target_radii).abs().mean()), int(done.sum()), B))
+            log("iter %3d  mean loss %.3e  mean chamfer %.3e  mean |r - r*| %.4f  converged %d / %d" %
+                (e, float(l.mean()), float(d.mean()), float((rad.detach() - target_radii).abs().mean()), int(done.sum()), B))
         if done.all():
             break
         with torch.no_grad():
@@ -483,8 +495,9 @@ def fit_pointcloud(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_p
     ident = torch.tensor([1.0, 0, 0, 0, 0.0, 5.0, 0.0], dtype=torch.float64).repeat(B, 1)
     target_pose = ident.clone() if target_pose is None else T(target_pose).reshape(B, 7)
     with torch.no_grad():
-        obs = pointcloud_observations(bounce_world(target_rad, run_time=run_time, shape=shape, corner_r=corner_r, init_pose=target_pose, **scene),
-                                      camera_pose(), noise=noise, every=every, run_time=run_time, seed=seed, observe=observe)
+        wt = bounce_world(target_rad, run_time=run_time, shape=shape, corner_r=corner_r, init_pose=target_pose, **scene)
+        tgt_cloud = chamfer_hip.pack([m[0] for m in wt.body_meshes])
+        obs = pointcloud_observations(wt, camera_pose(), noise=noise, every=every, run_time=run_time, seed=seed, observe=observe)
     rad = T(start_rad).reshape(-1).clone().requires_grad_()
     start_pose = target_pose.clone() if start_pose is None else T(start_pose).reshape(B, 7)
     rot, pos = start_pose[:, :4].clone().requires_grad_(optimize_pose), start_pose[:, 4:].clone().requires_grad_(optimize_pose)
@@ -507,9 +520,13 @@ def fit_pointcloud(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_p
             l, r_now = loss.detach().cpu().numpy(), rad.detach().numpy().copy()
             done |= (np.abs(last - l) < conv_thresh) & (np.abs(last_rad - r_now) < conv_thresh_shape)
             h.append(dict(iter=e, loss=l.copy(), rad=r_now, pose=pose0.detach().numpy().copy(), grad_rad=rad.grad.numpy().copy(), done=done.copy()))
+            cd = ""
+            if stage == "trajectory":      # (the first-frame stage builds no world, so it has no mesh of the estimate at hand)
+                h[-1]["chamfer"] = _chamfer_series([m[0] for m in world.body_meshes], tgt_cloud)
+                cd = "  mean chamfer %.3e" % float(h[-1]["chamfer"].mean())
             if log:
-                log("[%s] iter %3d  mean loss %.3e  mean |rad - rad*| %.4f  mean |pos - pos*| %.4f  converged %d / %d" %
-                    (stage, e, float(l.mean()), float(np.abs(r_now - target_rad.numpy()).mean()),
+                log("[%s] iter %3d  mean loss %.3e%s  mean |rad - rad*| %.4f  mean |pos - pos*| %.4f  converged %d / %d" %
+                    (stage, e, float(l.mean()), cd, float(np.abs(r_now - target_rad.numpy()).mean()),
                      float((pos.detach() - target_pose[:, 4:]).norm(dim=1).mean()), int(done.sum()), B))
             if done.all():
                 break
@@ -914,8 +931,10 @@ def bounce_world_latent(latents, packed, use_toc_diff=True, use_friction=True, u
         params = {key: torch.cat([prm[:, :s_], mine], 1), "inertia": torch.cat([inertia[:, :s_], torch.stack(Is)[:, None]], 1),
                   "verts": torch.cat([v.to(dev) for v in vts])}
     steps = int(math.ceil(run_time / dt)) + 2
-    return BatchWorld3D(spec, params=params, dt=dt, time_of_contact_diff=use_toc_diff, strict_no_penetration=False,
-                        max_substeps=8 * steps + 64, device=device, maxc=256, max_cand=8192, max_pc=128)
+    w = BatchWorld3D(spec, params=params, dt=dt, time_of_contact_diff=use_toc_diff, strict_no_penetration=False,
+                     max_substeps=8 * steps + 64, device=device, maxc=256, max_cand=8192, max_pc=128)
+    w.body_meshes = spec["meshes"][-B:]      # the thrown body's mesh per scene, as bounce_world keeps it
+    return w
 
 
 def fit_trajectory_latent(target_latents, start_latents, packed, run_time=1.0, max_iter=100, lr=1e-3, conv_thresh=1e-5,
@@ -924,8 +943,9 @@ def fit_trajectory_latent(target_latents, start_latents, packed, run_time=1.0, m
     latent_reg 1e-4): the latent code is fitted so that the thrown body's trajectory (its positions at the nearest target
     times, trajectory_loss) matches the target's; loss = trajectory_loss + latent_reg |latent|^2."""
     with torch.no_grad():
-        target = run_world_fixed_dt(bounce_world_latent(torch.as_tensor(np.asarray(target_latents, np.float64)), packed,
-                                                        run_time=run_time, **scene), run_time)
+        wt = bounce_world_latent(torch.as_tensor(np.asarray(target_latents, np.float64)), packed, run_time=run_time, **scene)
+        target = run_world_fixed_dt(wt, run_time)
+        tgt_cloud = chamfer_hip.pack([m[0] for m in wt.body_meshes])
     lat = torch.tensor(np.asarray(start_latents, np.float64), requires_grad=True)
     opt = torch.optim.Adam([lat], lr=lr) if optimizer == "Adam" else torch.optim.SGD([lat], lr=lr)
     hist, last = [], None
@@ -937,10 +957,11 @@ def fit_trajectory_latent(target_latents, start_latents, packed, run_time=1.0, m
         loss = loss + latent_reg * (lat.to(loss.device) ** 2).sum(dim=1)
         loss.sum().backward()
         l = loss.detach().cpu().numpy()
-        hist.append(dict(iter=e, loss=l.copy(), latent=lat.detach().numpy().copy(), grad=lat.grad.numpy().copy()))
+        d = _chamfer_series([m[0] for m in world.body_meshes], tgt_cloud)
+        hist.append(dict(iter=e, loss=l.copy(), latent=lat.detach().numpy().copy(), grad=lat.grad.numpy().copy(), chamfer=d))
         if log:
-            log("iter %3d  mean loss %.3e  mean |latent - target| %.4f  |grad| %.3e" %
-                (e, float(l.mean()), float(np.abs(lat.detach().numpy() - np.asarray(target_latents)).mean()), float(lat.grad.abs().mean())))
+            log("iter %3d  mean loss %.3e  mean chamfer %.3e  mean |latent - target| %.4f  |grad| %.3e" %
+                (e, float(l.mean()), float(d.mean()), float(np.abs(lat.detach().numpy() - np.asarray(target_latents)).mean()), float(lat.grad.abs().mean())))
         if last is not None and np.all(np.abs(last - l) < conv_thresh):
             break
         opt.step()
@@ -952,21 +973,25 @@ def fit_trajectory_latent(target_latents, start_latents, packed, run_time=1.0, m
 def spin_world(latents, torque_dirs, packed, scale=1.0, mass=1.0, res=128, steps=64, device=None, keep_meshes=True):
     """optim_shapespace.py:71-92 for one scene per latent code: a single neural-SDF body (scale 1) whose translation is locked
     by X/Y/Z constraints; no contacts, so only its inertia matters -- integrated over its level-set mesh (MeshSDF:
-    differentiable w.r.t. the latent).  The torque (t < 0.3) is applied by the caller through world.params['fext']."""
+    differentiable w.r.t. the latent).  The torque (t < 0.3) is applied by the caller through world.params['fext'].
+    keep_meshes='device': world.meshes as with False, the vertices stay on the device as world.mesh_verts (what the chamfer
+    distance of the report reads)."""
     B = latents.shape[0]
-    Is, ms = [], []
+    Is, ms, vs = [], [], []
     for s in range(B):
         v, f = meshsdf.igr_mesh(latents[s], packed, res=res)
         vt = v * scale
         Is.append(mass_properties.mesh_inertia_diff(vt, f, torch.tensor(float(mass), dtype=torch.float64)))
         # (the meshes are only kept for the chamfer distance of the experiment's report; a caller that does not need them saves
         # a device -> host copy of ~1 MB and a synchronisation per scene)
-        ms.append((vt.detach().cpu().numpy(), f.cpu().numpy()) if keep_meshes else (None, int(f.shape[0])))
-    return _spin_world(torch.stack(Is), ms, scale, mass, steps, device)
+        ms.append((vt.detach().cpu().numpy(), f.cpu().numpy()) if keep_meshes is True else (None, int(f.shape[0])))
+        vs.append(vt.detach())
+    return _spin_world(torch.stack(Is), ms, scale, mass, steps, device, vs if keep_meshes else None)
 
 
-def _spin_world(inertias, ms, scale, mass, steps, device):
-    """One free-spinning body per scene with the given body-frame inertia tensors [B, 3, 3] (graph kept) and meshes."""
+def _spin_world(inertias, ms, scale, mass, steps, device, verts=None):
+    """One free-spinning body per scene with the given body-frame inertia tensors [B, 3, 3] (graph kept) and meshes; verts: the
+    meshes' vertices per scene as tensors of any device (world.mesh_verts; default: those of `ms`)."""
     B = len(ms)
     inertia = inertias[:, None]                                               # [B,1,3,3], graph to the shape parameters
     one = lambda a: np.tile(np.asarray(a, np.float64), (B, 1, 1))
@@ -980,6 +1005,7 @@ def _spin_world(inertias, ms, scale, mass, steps, device):
                 Je=np.tile(np.concatenate([np.zeros((3, 3)), np.eye(3)], 1), (B, 1, 1)), no_contact=np.zeros((1, 1), np.uint8))
     w = BatchWorld3D(spec, params=dict(inertia=inertia), max_substeps=steps + 16, device=device)
     w.meshes = ms
+    w.mesh_verts = verts if verts is not None else [m[0] for m in ms]
     return w
 
 
@@ -1016,19 +1042,20 @@ def fit_inertia_latent(target_latents, start_latents, torque_dirs, packed, run_t
     linear solve of every step."""
     steps = int(math.ceil(run_time / Defaults3D.DT)) + 2
     with torch.no_grad():
-        wt = spin_world(torch.as_tensor(target_latents, dtype=torch.float64), torque_dirs, packed, res=res, steps=steps)
+        wt = spin_world(torch.as_tensor(target_latents, dtype=torch.float64), torque_dirs, packed, res=res, steps=steps, keep_meshes="device")
         v_target = run_spin(wt, torque_dirs, run_time).clone()
+        tgt_cloud = chamfer_hip.pack(wt.mesh_verts)      # (once: the target's vertices of every scene, packed on the device)
     lat = torch.tensor(np.asarray(start_latents, np.float64), requires_grad=True)
     hist, last = [], None
     for e in range(max_iter):
         if lat.grad is not None:
             lat.grad = None
-        w = spin_world(lat, torque_dirs, packed, res=res, steps=steps)
+        w = spin_world(lat, torque_dirs, packed, res=res, steps=steps, keep_meshes="device")
         v = run_spin(w, torque_dirs, run_time)
         loss = ((v - v_target.to(v)) ** 2).sum(dim=1) + latent_reg * (lat.to(v.device) ** 2).sum(dim=1)
         loss.sum().backward()
         l = loss.detach().cpu().numpy()
-        d = np.array([float(chamfer(torch.as_tensor(a[0]), torch.as_tensor(b[0]))) for a, b in zip(w.meshes, wt.meshes)])
+        d = _chamfer_series(w.mesh_verts, tgt_cloud)
         hist.append(dict(iter=e, loss=l.copy(), latent=lat.detach().numpy().copy(), grad=lat.grad.numpy().copy(), chamfer=d))
         if log:
             log("iter %3d  mean loss %.3e  mean chamfer %.3e  |grad| %.3e" % (e, float(l.mean()), float(d.mean()), float(lat.grad.abs().mean())))
@@ -1050,6 +1077,7 @@ def fit_inertia_primitive(kind, target_dims, start_dims, torque_dirs, run_time=2
     with torch.no_grad():
         wt = primitive_spin_world(kind, tgt, steps=steps)
         v_target = run_spin(wt, torque_dirs, run_time).clone()
+        tgt_cloud = chamfer_hip.pack(wt.mesh_verts)
     dims = torch.tensor(np.asarray(start_dims, np.float64).reshape(-1, PRIMITIVES[kind]), requires_grad=True)
     opt = torch.optim.Adam([dims], lr=lr) if optimizer == "Adam" else torch.optim.SGD([dims], lr=lr)
     hist, last = [], None
@@ -1060,7 +1088,7 @@ def fit_inertia_primitive(kind, target_dims, start_dims, torque_dirs, run_time=2
         loss = ((v - v_target.to(v)) ** 2).sum(dim=1)
         loss.sum().backward()
         l = loss.detach().cpu().numpy()
-        d = np.array([float(chamfer(torch.as_tensor(a[0]), torch.as_tensor(b[0]))) for a, b in zip(w.meshes, wt.meshes)])
+        d = _chamfer_series(w.mesh_verts, tgt_cloud)
         hist.append(dict(iter=e, loss=l.copy(), dims=dims.detach().numpy().copy(), grad=dims.grad.numpy().copy(), chamfer=d))
         if log:
             log("iter %3d  mean loss %.3e  mean chamfer %.3e  mean |dims - target| %.4f" %

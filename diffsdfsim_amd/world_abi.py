@@ -50,6 +50,8 @@ OPTIONAL_PROTOTYPES = {
     # recorded clouds (csrc/cloud_select.h; exported by every product library, diffsdfsim_amd/recorded.py raises where not)
     "dss_cloud_select_count": ("i", "iiiipppp"), "dss_cloud_select_emit": ("i", "iiiippppp"),
     "dss_cloud_stats_workspace_bytes": ("z", "ii"), "dss_cloud_stats": ("i", "iippppzp"),
+    # chamfer distance (csrc/chamfer.h; exported by every product library, diffsdfsim_amd/chamfer.py raises where not)
+    "dss_chamfer_nn_workspace_bytes": ("z", "iii"), "dss_chamfer_nn": ("i", "iiipppppppzp"), "dss_chamfer_segment_mean": ("i", "ipppp"),
     "dss_diag_set_lcp_stamps": ("v", "pp"), "dss_diag_set_np_stamps": ("v", "pp"), "dss_diag_latency": ("v", "iiippppp"),
     "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"],
 }

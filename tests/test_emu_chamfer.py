@@ -1,0 +1,140 @@
+"""CPU: csrc/chamfer.hip through the emulator (the kernels, their launch shape, LDS tiles, the split of the reference range and
+the merge of its partials as on the device) against the numpy reference of tests/chamfer_ref.py, whose docstring derives the
+bounds: idx equal to argmin, d2 within 2^-48 relative, both exact on the integer lattice.
+
+Which path a call takes is the launcher's rule of csrc/chamfer.h, mirrored by chamfer.splits: splits = min(ceil(tiles /
+SPLIT_TILES), ceil(TARGET_WG / (nseg * query blocks))).  At these small grids the second term is large, so a call is split --
+partials to the workspace, merge kernel -- exactly when its longest reference segment has more than SPLIT_TILES tiles.
+tests/emu/check_chamfer.cpp walks the same shapes as a program of its own under the address and undefined-behaviour sanitizers."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import chamfer_ref as ref
+from diffsdfsim_amd import chamfer
+from emu import emu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+Q, T = chamfer.QUERIES, chamfer.TILE
+_c = lambda a, dt=np.float64: np.ascontiguousarray(a, dtype=dt)
+_p = lambda a: a.ctypes.data if a.size else None
+
+
+def nearest(q, q_off, r, r_off, fill=-7.0):
+    L = emu.lib()
+    q, r, qo, ro = _c(q), _c(r), _c(q_off, np.int32), _c(r_off, np.int32)
+    nseg, max_q, max_r = len(qo) - 1, int(np.diff(qo).max()), int(np.diff(ro).max())
+    nbytes = L.dss_chamfer_nn_workspace_bytes(nseg, max_q, max_r)
+    assert (nbytes > 0) == (chamfer.splits(nseg, max_q, max_r) > 1)
+    ws = np.zeros(nbytes // 8 + 1)
+    d2, idx = np.full(len(q) + 1, fill), np.full(len(q) + 1, -7, np.int32)      # (one more: nothing may be written past the last query)
+    rc = L.dss_chamfer_nn(nseg, max_q, max_r, qo.ctypes.data, _p(q), ro.ctypes.data, _p(r), d2.ctypes.data, idx.ctypes.data, ws.ctypes.data, nbytes, None)
+    assert rc == 0 and d2[-1] == fill and idx[-1] == -7
+    return d2[:-1], idx[:-1]
+
+
+def test_python_constants_are_the_headers():
+    text = open(os.path.join(HERE, "..", "diffsdfsim_amd", "csrc", "chamfer.h")).read()
+    got = {k: int(v) for k, v in re.findall(r"#define DSS_CHAMFER_(\w+) (\d+)", text)}
+    assert got == dict(TILE=chamfer.TILE, QUERIES=chamfer.QUERIES, SPLIT_TILES=chamfer.SPLIT_TILES, TARGET_WG=chamfer.TARGET_WG)
+
+
+@pytest.mark.parametrize("shift", [None, ref.SHIFT], ids=["origin", "shifted"])
+@pytest.mark.parametrize("path", ["direct", "split"])
+def test_nine_unequal_segments_across_every_boundary(path, shift):
+    lens = ref.segment_cases(Q, T)[path]
+    q, qo, r, ro = ref.random_clouds([a for a, _ in lens], [b for _, b in lens], seed=11, shift=shift)
+    assert (chamfer.splits(len(lens), max(a for a, _ in lens), max(b for _, b in lens)) > 1) == (path == "split")
+    d2, idx = nearest(q, qo, r, ro)
+    ref.check_nn(d2, idx, q, qo, r, ro)
+    assert np.all(d2[qo[5]:qo[6]] == np.inf) and np.all(idx[qo[5]:qo[6]] == -1)      # the segment without reference points
+    again = nearest(q, qo, r, ro, fill=3.0)
+    assert np.array_equal(d2, again[0]) and np.array_equal(idx, again[1])
+
+
+def test_few_queries_against_three_tiles_and_one_take_the_split_path():
+    # one segment, one query block: ceil(TARGET_WG / 1) is far above ceil(4 tiles / SPLIT_TILES) = 2 splits of 2 tiles
+    assert chamfer.splits(1, 5, 3 * T + 1) == 2 and chamfer.splits(1, 5, 5 * T + 1) == 3
+    for nr, seed in ((3 * T + 1, 5), (5 * T + 1, 6)):
+        q, qo, r, ro = ref.random_clouds([5], [nr], seed=seed)
+        d2, idx = nearest(q, qo, r, ro)
+        ref.check_nn(d2, idx, q, qo, r, ro)
+        assert idx.max() >= 2 * T or nr > 3 * T + 1      # (seed 5: some winner lies in the second split)
+
+
+@pytest.mark.parametrize("nr", [2 * T, 3 * T + 1, 5 * T + 1], ids=["direct", "split2", "split3"])
+def test_integer_lattice_is_exact_and_ties_keep_the_lowest_index(nr):
+    q, r = ref.lattice_clouds(Q + 65, nr, seed=3)
+    qo, ro = [0, len(q)], [0, len(r)]
+    d2, idx = nearest(q, qo, r, ro)
+    ref.check_nn(d2, idx, q, np.asarray(qo), r, np.asarray(ro), exact=True)
+    d = ref.dist2(q, r)
+    tied = d == d.min(1, keepdims=True)
+    first, last = tied.argmax(1), d.shape[1] - 1 - tied[:, ::-1].argmax(1)
+    per_split = -(-(-(-nr // T)) // chamfer.splits(1, len(q), nr)) * T
+    assert np.any(last // T > first // T) and (nr == 2 * T or np.any(last // per_split > first // per_split))      # ties across tiles, across splits
+
+
+def test_segment_mean_in_a_fixed_order():
+    L = emu.lib()
+    rng = np.random.default_rng(2)
+    off = _c(np.concatenate([[0], np.cumsum([1, 0, 63, 257, 1025])]), np.int32)
+    v, out = rng.uniform(0, 1, off[-1]), np.full(5, -7.0)
+    assert L.dss_chamfer_segment_mean(5, off.ctypes.data, v.ctypes.data, out.ctypes.data, None) == 0
+    for s in range(5):
+        seg = v[off[s]:off[s + 1]]
+        if len(seg) == 0:
+            assert np.isnan(out[s])
+        else:
+            assert abs(out[s] - seg.mean()) <= len(seg) * 2.0 ** -52 * seg.mean()
+    assert L.dss_chamfer_segment_mean(0, off.ctypes.data, v.ctypes.data, out.ctypes.data, None) == -1
+    assert L.dss_chamfer_segment_mean(5, None, v.ctypes.data, out.ctypes.data, None) == -1
+    assert L.dss_chamfer_segment_mean(5, off.ctypes.data, None, out.ctypes.data, None) == -1
+    assert L.dss_chamfer_segment_mean(5, off.ctypes.data, v.ctypes.data, None, None) == -1
+
+
+def test_return_codes_leave_the_outputs_untouched():
+    L = emu.lib()
+    q, qo, r, ro = ref.random_clouds([5], [3 * T + 1], seed=5)
+    qo, ro = _c(qo, np.int32), _c(ro, np.int32)
+    d2, idx = np.full(5, -7.0), np.full(5, -7, np.int32)
+    nb = L.dss_chamfer_nn_workspace_bytes(1, 5, 3 * T + 1)
+    assert nb == 1 * 2 * 5 * 12
+    ws = np.zeros(nb // 8 + 1)
+    A = dict(nseg=1, mq=5, mr=3 * T + 1, qo=qo.ctypes.data, q=q.ctypes.data, ro=ro.ctypes.data, r=r.ctypes.data, d2=d2.ctypes.data, idx=idx.ctypes.data,
+             ws=ws.ctypes.data, nb=nb)
+    call = lambda **kw: L.dss_chamfer_nn(*[{**A, **kw}[k] for k in ("nseg", "mq", "mr", "qo", "q", "ro", "r", "d2", "idx", "ws", "nb")], None)
+    for bad in (dict(nseg=0), dict(mq=-1), dict(mr=-1), dict(qo=None), dict(q=None), dict(ro=None), dict(r=None), dict(d2=None), dict(idx=None)):
+        assert call(**bad) == -1, bad                                  # DSS_E_BADARG
+    assert call(ws=None) == -2 and call(nb=nb - 1) == -2               # DSS_E_WORKSPACE
+    assert call(nseg=2 ** 22, mq=2 ** 10) == -3                        # DSS_E_UNSUPPORTED: nseg * max_q_len = 2^32 rows
+    assert call(nseg=2 ** 22, mq=1, mr=2 ** 10) == -3                  # nseg * max_r_len
+    assert call(nseg=2 ** 30, mq=1, mr=1) == -3                        # the merge-sized grid nseg * query blocks * QUERIES / 256
+    assert call(mr=2 ** 31 - 1) == -3                                  # the end of the last split past an int
+    assert L.dss_chamfer_nn_workspace_bytes(0, 5, 5) == 0 and L.dss_chamfer_nn_workspace_bytes(1, 5, 2 * T) == 0
+    assert np.all(d2 == -7.0) and np.all(idx == -7)
+    # max_q_len = 0 (only empty query segments) and max_r_len = 0 (no reference point anywhere) are valid and need no workspace
+    z = _c([0, 0], np.int32)
+    assert call(mq=0, qo=z.ctypes.data, q=None, ws=None, nb=0) == 0 and np.all(d2 == -7.0)
+    assert call(mr=0, ro=z.ctypes.data, r=None, ws=None, nb=0) == 0 and np.all(d2 == np.inf) and np.all(idx == -1)
+
+
+def test_stand_alone_program_under_the_sanitizers():
+    out = os.path.join(HERE, "emu", "_build")
+    os.makedirs(out, exist_ok=True)
+    exe = os.path.join(out, "check_chamfer")
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-w", "-I", os.path.join(HERE, "emu"), "-I", os.path.join(HERE, "..", "diffsdfsim_amd", "csrc"),
+           "-o", exe, os.path.join(HERE, "emu", "check_chamfer.cpp")]
+    san = subprocess.run(cmd + ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], capture_output=True, text=True)
+    if san.returncode != 0:
+        # only a link without the sanitizers' runtimes may fall back to a plain build; any other failure is the program's
+        assert "cannot find" in san.stderr and ("asan" in san.stderr or "ubsan" in san.stderr), san.stderr[-2000:]
+        subprocess.check_call(cmd)
+    print("check_chamfer built %s the sanitizers" % ("with" if san.returncode == 0 else "WITHOUT"))
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    w = r.stdout.split()
+    assert int(w[0]) == 7 and int(w[2]) > 0, r.stdout      # calls walked, queries checked
