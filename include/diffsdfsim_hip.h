@@ -405,7 +405,8 @@ int dss_selftest_sqrt(const double *x, int n, int *mismatches, void *stream);
  *   The workspace passed to dss_mc_emit must be the one dss_mc_count filled.
  *   dss_meshsdf_backward: grad_prm[4] = sum_v -(grad_verts[v] . n_v) d phi / d unit_prm (v), analytic primitives,
  *   unit frame of the reference (unit_prm [4] host = the three parameters and the corner radius, already divided by the
- *   body scale; vertices in [-1,1]^3). */
+ *   body scale; vertices in [-1,1]^3).  n_v = the normalised derivative of the SDF w.r.t. the point, as autograd gives it
+ *   to the reference (bodies.py:687-689); for the brick that is not the body's grad_func. */
 size_t dss_mc_workspace_bytes(int n0, int n1, int n2);
 int dss_mc_count(const double *phi, int n0, int n1, int n2, double iso, const int *ntri_tab, void *workspace,
                  size_t workspace_bytes, int *totals, void *stream);

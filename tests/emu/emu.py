@@ -15,8 +15,8 @@ _LIB = None
 
 def lib():
     global _LIB
-    subprocess.check_call(["make", "-s", "-C", _HERE])
-    if _LIB is None:
+    if _LIB is None:        # (once per process: a library that is loaded is not rebuilt under the process)
+        subprocess.check_call(["make", "-s", "-C", _HERE])
         _LIB = world_abi.bind(ctypes.CDLL(os.path.join(_HERE, "_build", "libdss_emu.so")))
     return _LIB
 
@@ -165,6 +165,19 @@ def mesh_inertia(verts, faces, mass):
     return J.reshape(3, 3), vol[0]
 
 
+def mesh_inertia_batch(verts, faces, masses):
+    """dss_mesh_inertia on one pooled table: lists of meshes -> J [nmesh,3,3], vol [nmesh] (non-zero voff / foff)."""
+    L = lib()
+    V = _c(np.concatenate([np.asarray(v, np.float64) for v in verts])); F = _c(np.concatenate(list(faces)), np.int32)
+    voff = _c(np.cumsum([0] + [len(v) for v in verts[:-1]]), np.int32)
+    foff = _c(np.cumsum([0] + [len(f) for f in faces[:-1]]), np.int32)
+    nf = _c([len(f) for f in faces], np.int32)
+    M = _c(masses); J = np.zeros((len(verts), 9)); vol = np.zeros(len(verts))
+    rc = L.dss_mesh_inertia(_p(V), _p(F), _p(voff), _p(foff), _p(nf), len(verts), _p(M), _p(J), _p(vol), None)
+    assert rc == 0
+    return J.reshape(-1, 3, 3), vol
+
+
 def marching_cubes(phi, iso=0.0):
     L = lib()
     ntri, tri, _ = mc_tables.tables()
@@ -181,18 +194,20 @@ def marching_cubes(phi, iso=0.0):
 
 
 def meshsdf_backward(shape_type, unit_prm, unit_verts, gbar):
+    """-> the gradient w.r.t. the first three unit parameters, and w.r.t. the fourth (corner radius) when one is passed."""
     L = lib()
     k = np.asarray(unit_prm).size
     prm = _c(np.concatenate([np.asarray(unit_prm, np.float64).reshape(-1), np.zeros(4)])[:4])
     V = _c(unit_verts); Gb = _c(gbar); out = np.zeros(4)
     rc = L.dss_meshsdf_backward(int(shape_type), _p(prm), _p(V), _p(Gb), len(V), _p(out), None)
     assert rc == 0
-    return out[:max(k, 3)]
+    return out[:4] if k >= 4 else out[:3]
 
 
-def mesh_inertia_backward(verts, faces, mass, gJ):
+def mesh_inertia_backward(verts, faces, mass, gJ, fill=0.0):
+    """fill: what the output buffer holds before the call (the kernel has to clear it itself)."""
     L = lib()
-    V = _c(verts); F = _c(faces, np.int32); g = _c(gJ).reshape(9); out = np.zeros_like(V)
+    V = _c(verts); F = _c(faces, np.int32); g = _c(gJ).reshape(9); out = np.full_like(V, fill)
     rc = L.dss_mesh_inertia_backward(_p(V), _p(F), len(V), len(F), mass, _p(g), _p(out), None)
     assert rc == 0
     return out
