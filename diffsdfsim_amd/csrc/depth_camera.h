@@ -34,6 +34,42 @@ int dss_depth_render(int nview, int nbody, const double *pose, const int *shape_
                      double fx, double fy, double cx, double cy, int W, int H, double znear, double zfar, double *depth,
                      int *seg, void *stream);
 
+/* Voxel-grid bodies in the camera.  The grids are pooled as in DssWorld: grid_off [ngrid] (offset of grid g's samples in
+ * grid_data, in doubles), grid_dims [ngrid][3] (n0, n1, n2 >= 2 samples per axis, x slowest), grid_data.  Grid g's field at the
+ * body-frame point p is scale * trilinear(samples) at index position (p / scale + 1) / 2 * (n_d - 1), the cell index clamped
+ * to [0, n_d - 2]: the value of geom.h's SHAPE_GRID branch (scale = prm[3] of the body).
+ *
+ * dss_grid_block_min: for every block of DSS_GRID_BLOCK cells per axis (the last block of an axis may be partial) the least of
+ * the block's corner samples (up to 5 x 5 x 5).  Grid g has prod_d ceil((n_d - 1) / DSS_GRID_BLOCK) blocks, x slowest;
+ * blk_off [ngrid] are the caller's prefix sums of those counts, nblk their total, blk_min [nblk] the output.  The interpolant is
+ * a convex combination of a cell's corners, so a block whose minimum is positive holds no point of the surface -- for any
+ * samples; nothing is assumed about their Lipschitz constant. */
+#define DSS_GRID_BLOCK 4
+int dss_grid_block_min(int ngrid, const int *grid_off, const int *grid_dims, const double *grid_data, const int *blk_off, int nblk,
+                       double *blk_min, void *stream);
+
+/* dss_depth_render with grid bodies: grid_id [nview][nbody], the grid of a body of type DSS_SHAPE_GRID or DSS_SHAPE_IGR (a neural
+ * body is seen through the value grid its mesh is extracted from), read for those two types only.  Types 0-3 are traced as in
+ * dss_depth_render, by the same code.  A grid body's ray is clipped against the query cube like any other, taken into index
+ * coordinates and walked cell by cell (a 3-D DDA on two levels: a block whose blk_min is positive is left in one step).  Every
+ * plane crossing comes from the plane's integer index, t = (k - x0_d) / dx_d, so the walk visits at most n0 + n1 + n2 cells: a
+ * grid trace has no iteration cap and never gives seg = -2.  In a cell the 8 corners are loaded once and the interpolant is
+ * evaluated at the parameters where the ray enters and leaves it.
+ *   - the value at the slab entry is <= 0: a hit there;
+ *   - otherwise the first cell with entry value > 0 and exit value <= 0 holds the hit: bisection on the 8 corners until the
+ *     bracket is 4 ulp of t wide (at most 60 halvings), the end whose value is <= 0 is returned;
+ *   - a dip below zero strictly inside ONE cell, both ends positive (the ray clips a corner of the surface within a cell), is
+ *     not a hit: such a sliver is thinner than a cell, below the grid's resolution, as it is for marching cubes, whose
+ *     triangles replace the interpolant's surface within a cell by planes.
+ * Nearest hit, ties and outputs as in dss_depth_render; no atomics, the same bits in every call.  Brick, bowl, and a grid or
+ * neural body with grid_id = -1 give DSS_E_UNSUPPORTED and leave the outputs untouched; a grid_id >= ngrid or a dim < 2 gives
+ * DSS_E_BADARG.  The host reads shape_type, grid_id and grid_dims (and waits for the stream) before it enqueues; when no body
+ * has a grid it enqueues dss_depth_render's own kernel. */
+int dss_depth_render_grids(int nview, int nbody, const double *pose, const int *shape_type, const double *prm, const double *cam,
+                           double fx, double fy, double cx, double cy, int W, int H, double znear, double zfar, const int *grid_id,
+                           int ngrid, const int *grid_off, const int *grid_dims, const double *grid_data, const int *blk_off,
+                           const double *blk_min, double *depth, int *seg, void *stream);
+
 /* The observed points of body `body` in nview depth / segment images: lines 168-187 of match_pointcloud
  * (experiments/trajectory_fitting/optim_pointcloud.py).  A pixel is selected if it and its four edge neighbours have
  * seg == body (scipy.ndimage.binary_erosion with its default structure; beyond the image border counts as unset) and its

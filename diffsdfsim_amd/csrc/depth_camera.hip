@@ -7,6 +7,10 @@
 //                             nbody threads build the view's body table (R, pos, Shape<double>) in LDS.  Per body: ray into
 //                             the body frame, slab test against the query cube (the cheap rejection), sphere tracing of
 //                             query_sdf from the entry point; the nearest hit so far bounds the later bodies' traces.
+//   dss_depth_render_grids    the same with voxel-grid bodies (SHAPE_GRID, and SHAPE_IGR seen through its value grid): a kernel
+//                             of its own, the same per-pixel body compiled with the grid trace in it (dc_pixel<true>); a grid is
+//                             walked cell by cell by a two-level 3-D DDA over the block minima of dss_grid_block_min
+//   dss_grid_block_min        a thread per block of 4 x 4 x 4 cells: the least of its 5 x 5 x 5 corner samples
 //   dss_depth_points_count    a wavefront per image row, 64 columns at a time: ballot of the selected pixels, popcount
 //   dss_depth_points_emit     the same walk; a selected pixel's slot is the row's offset + the popcount of the lanes below it
 //
@@ -65,15 +69,124 @@ template <int TYPE> __device__ __forceinline__ int dc_trace(const DcBody &B, con
     return DC_CAP;
 }
 
-__global__ void __launch_bounds__(DC_THREADS) depth_render_kernel(int nbody, int tiles_x, int tiles_per_view, const double *__restrict__ pose,
-                                                                 const int *__restrict__ shape_type, const double *__restrict__ prm,
-                                                                 const double *__restrict__ cam, double fx, double fy, double cx, double cy,
-                                                                 int W, int H, double znear, double zfar, double *__restrict__ depth,
-                                                                 int *__restrict__ seg)
+// ---- voxel-grid bodies ---------------------------------------------------------------------------------------------------
+constexpr int GB = DSS_GRID_BLOCK;      // cells per block edge of dss_grid_block_min
+
+// a grid body of the view's table: its samples [n0][n1][n2] (x slowest), its block minima [nb0][nb1][nb2]; data == NULL: none
+struct DcGrid {
+    const double *data, *bmin;
+    int n[3], nb[3];
+};
+
+// The trilinear field of one cell along the ray, from its 8 corners in registers: v[4 dx + 2 dy + dz], cell index c, index
+// position xo + t xd.  (In units of the grid's samples: the caller compares with 0 only, the scale is positive.)
+struct DcCell {
+    double v[8];
+    __device__ __forceinline__ void load(const double *__restrict__ g, int n1, int n2, int c0, int c1, int c2)
+    {
+        const double *p = g + ((size_t)c0 * n1 + c1) * n2 + c2;
+        const size_t sx = (size_t)n1 * n2;
+        v[0] = p[0]; v[1] = p[1]; v[2] = p[n2]; v[3] = p[n2 + 1];
+        v[4] = p[sx]; v[5] = p[sx + 1]; v[6] = p[sx + n2]; v[7] = p[sx + n2 + 1];
+    }
+    __device__ __forceinline__ double at(double w0, double w1, double w2) const
+    {
+        const double u2 = 1.0 - w2, u1 = 1.0 - w1;
+        const double a = u2 * v[0] + w2 * v[1], b = u2 * v[2] + w2 * v[3], c = u2 * v[4] + w2 * v[5], d = u2 * v[6] + w2 * v[7];
+        return (1.0 - w0) * (u1 * a + w1 * b) + w0 * (u1 * c + w1 * d);
+    }
+};
+
+__device__ __forceinline__ int dc_floor_clamped(double u, int lo, int hi) { return (int)fmin(fmax(floor(u), (double)lo), (double)hi); }
+__device__ __forceinline__ int dc_imin(int a, int b) { return a < b ? a : b; }
+
+// One grid body along p(t) = ob + t db (body frame) for t in [t0, t1], both inside the query cube of half edge sc.
+// Index position x_d(t) = xo_d + t xd_d = (p_d / sc + 1) / 2 (n_d - 1).  The ray is walked cell by cell; every plane crossing is
+// computed from the plane's integer index, t = (k - xo_d) / xd_d, never by adding increments, and every iteration moves the cell
+// index of one axis by at least one in the direction of the ray while no other axis moves back: at most n0 + n1 + n2 iterations,
+// which is the loop's bound and not a cap (no status for it).  Blocks of GB cells whose corner minimum is positive are left in one
+// iteration: the interpolant is a convex combination of a cell's corners, so such a block holds no zero, whatever the field.
+// Invariant: the value at the entry of the current cell is > 0 (v_in; after a skipped block it is evaluated afresh).  The first
+// cell whose exit value is <= 0 holds the hit: bisection on its 8 corners until the bracket is 4 ulp of t wide, at most 60
+// halvings; the end whose value is <= 0 is returned.  A dip below zero inside one cell with both ends positive is not seen.
+__device__ __forceinline__ int dc_trace_grid(const DcGrid &G, double sc, const double *ob, const double *db, double t0, double t1,
+                                             double &t_hit)
 {
-    __shared__ DcBody tab[DC_MAX_BODY];
-    const int view = blockIdx.x / tiles_per_view, tile = blockIdx.x - view * tiles_per_view;
-    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x, tid = threadIdx.x;
+    const int n0 = G.n[0], n1 = G.n[1], n2 = G.n[2];
+    const double h0 = 0.5 * (n0 - 1), h1 = 0.5 * (n1 - 1), h2 = 0.5 * (n2 - 1);
+    const double xo0 = (ob[0] / sc + 1.0) * h0, xo1 = (ob[1] / sc + 1.0) * h1, xo2 = (ob[2] / sc + 1.0) * h2;
+    const double xd0 = db[0] / sc * h0, xd1 = db[1] / sc * h1, xd2 = db[2] / sc * h2;
+    const int s0 = xd0 > 0.0 ? 1 : (xd0 < 0.0 ? -1 : 0), s1 = xd1 > 0.0 ? 1 : (xd1 < 0.0 ? -1 : 0), s2 = xd2 > 0.0 ? 1 : (xd2 < 0.0 ? -1 : 0);
+    int c0 = dc_floor_clamped(xo0 + t0 * xd0, 0, n0 - 2), c1 = dc_floor_clamped(xo1 + t0 * xd1, 0, n1 - 2),
+        c2 = dc_floor_clamped(xo2 + t0 * xd2, 0, n2 - 2);
+    const double inf = 1.0 / 0.0;
+    double t_in = t0, v_in = 0.0;
+    bool fresh = true;      // v_in is not known for the current cell
+    int last_blk = -1;
+    DcCell cell;
+    for (int it = 0, bound = n0 + n1 + n2; it <= bound; ++it) {
+        const int b0 = c0 / GB, b1 = c1 / GB, b2 = c2 / GB, blk = (b0 * G.nb[1] + b1) * G.nb[2] + b2;
+        bool skip = false;
+        if (blk != last_blk) { last_blk = blk; skip = G.bmin[blk] > 0.0; }
+        // the planes through which the ray leaves the cell (the block, if it is skipped), by their integer indices
+        int k0, k1, k2;
+        if (skip) {
+            k0 = s0 > 0 ? dc_imin(GB * (b0 + 1), n0 - 1) : GB * b0;
+            k1 = s1 > 0 ? dc_imin(GB * (b1 + 1), n1 - 1) : GB * b1;
+            k2 = s2 > 0 ? dc_imin(GB * (b2 + 1), n2 - 1) : GB * b2;
+        } else {
+            k0 = c0 + (s0 > 0); k1 = c1 + (s1 > 0); k2 = c2 + (s2 > 0);
+        }
+        const double ta = s0 ? (k0 - xo0) / xd0 : inf, tb = s1 ? (k1 - xo1) / xd1 : inf, tc = s2 ? (k2 - xo2) / xd2 : inf;
+        const int axis = (ta <= tb && ta <= tc) ? 0 : (tb <= tc ? 1 : 2);
+        const double t_out = axis == 0 ? ta : (axis == 1 ? tb : tc);
+        const double t_ex = fmin(fmax(t_out, t_in), t1);
+        if (!skip) {
+            cell.load(G.data, n1, n2, c0, c1, c2);
+            if (fresh) {
+                v_in = cell.at(xo0 + t_in * xd0 - c0, xo1 + t_in * xd1 - c1, xo2 + t_in * xd2 - c2);
+                if (v_in <= 0.0) { t_hit = t_in; return DC_HIT; }      // the slab entry is inside the body (or the rounding of a block's face)
+                fresh = false;
+            }
+            const double v_out = cell.at(xo0 + t_ex * xd0 - c0, xo1 + t_ex * xd1 - c1, xo2 + t_ex * xd2 - c2);
+            if (v_out <= 0.0) {
+                double lo = t_in, hi = t_ex;
+                for (int h = 0; h < 60 && hi - lo > 8.881784197001252e-16 * hi; ++h) {      // 4 ulp: 4 * 2^-52 relative
+                    const double mid = 0.5 * (lo + hi);
+                    if (cell.at(xo0 + mid * xd0 - c0, xo1 + mid * xd1 - c1, xo2 + mid * xd2 - c2) <= 0.0) hi = mid; else lo = mid;
+                }
+                t_hit = hi;
+                return DC_HIT;
+            }
+            v_in = v_out;
+        } else {
+            fresh = true;
+        }
+        if (!(t_out < t1)) return DC_MISS;      // the ray ends (the cube's far side, zfar or a nearer hit) inside this cell
+        // into the next cell: one past the plane on the leaving axis; after a skipped block the other two from the position,
+        // kept within the block and never behind where they were
+        if (skip) {
+            const double u0 = xo0 + t_ex * xd0, u1 = xo1 + t_ex * xd1, u2 = xo2 + t_ex * xd2;
+            const int e0 = dc_imin(GB * b0 + GB - 1, n0 - 2), e1 = dc_imin(GB * b1 + GB - 1, n1 - 2), e2 = dc_imin(GB * b2 + GB - 1, n2 - 2);
+            const int m0 = s0 > 0 ? dc_floor_clamped(u0, c0, e0) : (s0 < 0 ? dc_floor_clamped(u0, GB * b0, c0) : c0);
+            const int m1 = s1 > 0 ? dc_floor_clamped(u1, c1, e1) : (s1 < 0 ? dc_floor_clamped(u1, GB * b1, c1) : c1);
+            const int m2 = s2 > 0 ? dc_floor_clamped(u2, c2, e2) : (s2 < 0 ? dc_floor_clamped(u2, GB * b2, c2) : c2);
+            c0 = axis == 0 ? (s0 > 0 ? k0 : k0 - 1) : m0;
+            c1 = axis == 1 ? (s1 > 0 ? k1 : k1 - 1) : m1;
+            c2 = axis == 2 ? (s2 > 0 ? k2 : k2 - 1) : m2;
+        } else {
+            c0 += axis == 0 ? s0 : 0; c1 += axis == 1 ? s1 : 0; c2 += axis == 2 ? s2 : 0;
+        }
+        if (c0 < 0 || c0 > n0 - 2 || c1 < 0 || c1 > n1 - 2 || c2 < 0 || c2 > n2 - 2) return DC_MISS;      // out of the grid
+        t_in = t_ex;
+    }
+    return DC_MISS;      // (not reached: see the bound above)
+}
+
+// The view's body table in LDS, by the workgroup's first nbody threads (the caller's barrier follows).
+__device__ __forceinline__ void dc_table(DcBody *tab, int view, int nbody, int tid, const double *__restrict__ pose,
+                                         const int *__restrict__ shape_type, const double *__restrict__ prm)
+{
     if (tid < nbody) {
         const size_t b = (size_t)view * nbody + tid;
         DcBody &B = tab[tid];
@@ -81,7 +194,15 @@ __global__ void __launch_bounds__(DC_THREADS) depth_render_kernel(int nbody, int
         for (int i = 0; i < 3; ++i) B.pos[i] = pose[7 * b + 4 + i];
         make_shape(B.shape, shape_type[b], prm + 4 * b, prm[4 * b + 3]);
     }
-    __syncthreads();
+}
+
+// One pixel against the view's bodies (after the table's barrier).  GRIDS: bodies with a grid (gtab[j].data != NULL) are traced
+// through it; without, gtab is not read and the code is that of the analytic renderer alone.
+template <bool GRIDS> __device__ __forceinline__ void dc_pixel(const DcBody *tab, const DcGrid *gtab, int nbody, int view, int tile_x, int tile_y,
+                                                               int tid, const double *__restrict__ cam, double fx, double fy, double cx,
+                                                               double cy, int W, int H, double znear, double zfar,
+                                                               double *__restrict__ depth, int *__restrict__ seg)
+{
     const int wave = tid / WAVE, lane = tid & (WAVE - 1);
     const int col = tile_x * DC_TILE + (wave & 1) * 8 + (lane & 7), row = tile_y * DC_TILE + (wave >> 1) * 8 + (lane >> 3);
     if (col >= W || row >= H) return;      // (no barrier below)
@@ -122,12 +243,16 @@ __global__ void __launch_bounds__(DC_THREADS) depth_render_kernel(int nbody, int
         if (miss || !(t0 <= t1)) continue;
         double t_hit = 0.0;
         int got = DC_MISS;
-        switch (B.shape.type) {
-        case SHAPE_BOX: got = dc_trace<SHAPE_BOX>(B, ob, db, inv_len, t0, t1, t_hit); break;
-        case SHAPE_SPHERE: got = dc_trace<SHAPE_SPHERE>(B, ob, db, inv_len, t0, t1, t_hit); break;
-        case SHAPE_CYLINDER: got = dc_trace<SHAPE_CYLINDER>(B, ob, db, inv_len, t0, t1, t_hit); break;
-        case SHAPE_BOX_ROUNDED: got = dc_trace<SHAPE_BOX_ROUNDED>(B, ob, db, inv_len, t0, t1, t_hit); break;
-        default: break;      // (the launcher has refused every other type)
+        if (GRIDS && gtab[j].data) {
+            got = dc_trace_grid(gtab[j], sc, ob, db, t0, t1, t_hit);
+        } else {
+            switch (B.shape.type) {
+            case SHAPE_BOX: got = dc_trace<SHAPE_BOX>(B, ob, db, inv_len, t0, t1, t_hit); break;
+            case SHAPE_SPHERE: got = dc_trace<SHAPE_SPHERE>(B, ob, db, inv_len, t0, t1, t_hit); break;
+            case SHAPE_CYLINDER: got = dc_trace<SHAPE_CYLINDER>(B, ob, db, inv_len, t0, t1, t_hit); break;
+            case SHAPE_BOX_ROUNDED: got = dc_trace<SHAPE_BOX_ROUNDED>(B, ob, db, inv_len, t0, t1, t_hit); break;
+            default: break;      // (the launcher has refused every other type)
+            }
         }
         if (got == DC_CAP) capped = true;
         else if (got == DC_HIT && t_hit < best) { best = t_hit; who = j; }      // a tie stays with the lower index
@@ -135,6 +260,71 @@ __global__ void __launch_bounds__(DC_THREADS) depth_render_kernel(int nbody, int
     const size_t px = ((size_t)view * H + row) * W + col;
     depth[px] = (capped || who < 0) ? 0.0 : best;
     seg[px] = capped ? -2 : who;
+}
+
+__global__ void __launch_bounds__(DC_THREADS) depth_render_kernel(int nbody, int tiles_x, int tiles_per_view, const double *__restrict__ pose,
+                                                                 const int *__restrict__ shape_type, const double *__restrict__ prm,
+                                                                 const double *__restrict__ cam, double fx, double fy, double cx, double cy,
+                                                                 int W, int H, double znear, double zfar, double *__restrict__ depth,
+                                                                 int *__restrict__ seg)
+{
+    __shared__ DcBody tab[DC_MAX_BODY];
+    const int view = blockIdx.x / tiles_per_view, tile = blockIdx.x - view * tiles_per_view;
+    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x, tid = threadIdx.x;
+    dc_table(tab, view, nbody, tid, pose, shape_type, prm);
+    __syncthreads();
+    dc_pixel<false>(tab, nullptr, nbody, view, tile_x, tile_y, tid, cam, fx, fy, cx, cy, W, H, znear, zfar, depth, seg);
+}
+
+// the same with the view's grid bodies: grid_id [nview][nbody] into the pooled table (checked by the launcher)
+__global__ void __launch_bounds__(DC_THREADS) depth_render_grids_kernel(int nbody, int tiles_x, int tiles_per_view, const double *__restrict__ pose,
+                                                                       const int *__restrict__ shape_type, const double *__restrict__ prm,
+                                                                       const double *__restrict__ cam, double fx, double fy, double cx,
+                                                                       double cy, int W, int H, double znear, double zfar,
+                                                                       const int *__restrict__ grid_id, const int *__restrict__ grid_off,
+                                                                       const int *__restrict__ grid_dims, const double *__restrict__ grid_data,
+                                                                       const int *__restrict__ blk_off, const double *__restrict__ blk_min,
+                                                                       double *__restrict__ depth, int *__restrict__ seg)
+{
+    __shared__ DcBody tab[DC_MAX_BODY];
+    __shared__ DcGrid gtab[DC_MAX_BODY];
+    const int view = blockIdx.x / tiles_per_view, tile = blockIdx.x - view * tiles_per_view;
+    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x, tid = threadIdx.x;
+    dc_table(tab, view, nbody, tid, pose, shape_type, prm);
+    if (tid < nbody) {
+        const int ty = shape_type[(size_t)view * nbody + tid];
+        const int g = (ty == SHAPE_GRID || ty == SHAPE_IGR) ? grid_id[(size_t)view * nbody + tid] : -1;      // (an analytic body's id is not read)
+        DcGrid &G = gtab[tid];
+        G.data = g >= 0 ? grid_data + grid_off[g] : nullptr;
+        G.bmin = g >= 0 ? blk_min + blk_off[g] : nullptr;
+        for (int i = 0; i < 3; ++i) {
+            G.n[i] = g >= 0 ? grid_dims[3 * g + i] : 2;
+            G.nb[i] = (G.n[i] - 1 + GB - 1) / GB;
+        }
+    }
+    __syncthreads();
+    dc_pixel<true>(tab, gtab, nbody, view, tile_x, tile_y, tid, cam, fx, fy, cx, cy, W, H, znear, zfar, depth, seg);
+}
+
+// blk_min of every block of every grid: a thread per block, the least of its (up to) 5 x 5 x 5 corner samples
+__global__ void __launch_bounds__(DC_THREADS) grid_block_min_kernel(int ngrid, int nblk, const int *__restrict__ grid_off,
+                                                                   const int *__restrict__ grid_dims, const double *__restrict__ grid_data,
+                                                                   const int *__restrict__ blk_off, double *__restrict__ blk_min)
+{
+    const int t = blockIdx.x * DC_THREADS + threadIdx.x;
+    if (t >= nblk) return;
+    int g = 0;
+    while (g + 1 < ngrid && blk_off[g + 1] <= t) ++g;
+    const int n0 = grid_dims[3 * g], n1 = grid_dims[3 * g + 1], n2 = grid_dims[3 * g + 2];
+    const int nb1 = (n1 - 1 + GB - 1) / GB, nb2 = (n2 - 1 + GB - 1) / GB;
+    const int r = t - blk_off[g], b0 = r / (nb1 * nb2), b1 = (r / nb2) % nb1, b2 = r % nb2;
+    const int i1 = dc_imin(GB * b0 + GB, n0 - 1), j1 = dc_imin(GB * b1 + GB, n1 - 1), k1 = dc_imin(GB * b2 + GB, n2 - 1);
+    const double *G = grid_data + grid_off[g];
+    double m = G[((size_t)(GB * b0) * n1 + GB * b1) * n2 + GB * b2];
+    for (int i = GB * b0; i <= i1; ++i)
+        for (int j = GB * b1; j <= j1; ++j)
+            for (int k = GB * b2; k <= k1; ++k) m = fmin(m, G[((size_t)i * n1 + j) * n2 + k]);
+    blk_min[t] = m;
 }
 
 // is pixel (r, c) of the image at `base` an observed point of `body`: inside the mask eroded by one pixel, depth not 0
@@ -215,6 +405,63 @@ int dss_depth_render(int nview, int nbody, const double *pose, const int *shape_
             return DSS_E_UNSUPPORTED;      // brick, bowl: not shown to bound the distance; neural and grid bodies: not in this renderer
     hipLaunchKernelGGL(depth_render_kernel, dim3(tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, tiles_x, tiles_per_view, pose,
                        shape_type, prm, cam, fx, fy, cx, cy, W, H, znear, zfar, depth, seg);
+    return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
+}
+
+int dss_grid_block_min(int ngrid, const int *grid_off, const int *grid_dims, const double *grid_data, const int *blk_off, int nblk,
+                       double *blk_min, void *stream)
+{
+    if (ngrid <= 0 || nblk <= 0 || !grid_off || !grid_dims || !grid_data || !blk_off || !blk_min) return DSS_E_BADARG;
+    hipLaunchKernelGGL(grid_block_min_kernel, dim3((nblk + DC_THREADS - 1) / DC_THREADS), dim3(DC_THREADS), 0, (hipStream_t)stream, ngrid,
+                       nblk, grid_off, grid_dims, grid_data, blk_off, blk_min);
+    return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
+}
+
+int dss_depth_render_grids(int nview, int nbody, const double *pose, const int *shape_type, const double *prm, const double *cam,
+                           double fx, double fy, double cx, double cy, int W, int H, double znear, double zfar, const int *grid_id,
+                           int ngrid, const int *grid_off, const int *grid_dims, const double *grid_data, const int *blk_off,
+                           const double *blk_min, double *depth, int *seg, void *stream)
+{
+    if (nview <= 0 || nbody <= 0 || W <= 0 || H <= 0 || !pose || !shape_type || !prm || !cam || !depth || !seg || !grid_id || ngrid < 0)
+        return DSS_E_BADARG;
+    if (ngrid > 0 && (!grid_off || !grid_dims || !grid_data || !blk_off || !blk_min)) return DSS_E_BADARG;
+    if (!(fx != 0.0) || !(fy != 0.0) || !(znear >= 0.0) || !(znear < zfar)) return DSS_E_BADARG;
+    if (nbody > DC_MAX_BODY || !dc_images_ok(nview, H, W)) return DSS_E_UNSUPPORTED;
+    const int tiles_x = (W + DC_TILE - 1) / DC_TILE, tiles_per_view = tiles_x * ((H + DC_TILE - 1) / DC_TILE);
+    if ((long long)tiles_per_view * nview > 0x7fffffffLL) return DSS_E_UNSUPPORTED;      // grid.x
+    // shape types, grid ids and the grids' dims decide the status, so the host reads them before anything is enqueued
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ntype = (size_t)nview * nbody;
+#if defined(DSS_EMU)
+    const int *types = shape_type, *ids = grid_id, *dims = grid_dims;      // (the emulator's device memory is the host's)
+#else
+    std::vector<int> host_types(ntype), host_ids(ntype), host_dims(3 * (size_t)ngrid);
+    if (hipMemcpyAsync(host_types.data(), shape_type, sizeof(int) * ntype, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(host_ids.data(), grid_id, sizeof(int) * ntype, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (ngrid > 0 && hipMemcpyAsync(host_dims.data(), grid_dims, sizeof(int) * 3 * (size_t)ngrid, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return DSS_E_BADARG;
+    const int *types = host_types.data(), *ids = host_ids.data(), *dims = host_dims.data();
+#endif
+    for (int g = 0; g < 3 * ngrid; ++g)
+        if (dims[g] < 2) return DSS_E_BADARG;
+    bool any = false;
+    for (size_t i = 0; i < ntype; ++i) {
+        const bool level_set = types[i] == DSS_SHAPE_GRID || types[i] == DSS_SHAPE_IGR;
+        if (level_set && ids[i] >= ngrid) return DSS_E_BADARG;
+        if (level_set && ids[i] < 0) return DSS_E_UNSUPPORTED;      // a grid or neural body without a grid
+        if (!level_set && types[i] != DSS_SHAPE_BOX && types[i] != DSS_SHAPE_SPHERE && types[i] != DSS_SHAPE_CYLINDER &&
+            types[i] != DSS_SHAPE_BOX_ROUNDED)
+            return DSS_E_UNSUPPORTED;      // brick, bowl: as in dss_depth_render
+        if (level_set) any = true;
+    }
+    if (any)
+        hipLaunchKernelGGL(depth_render_grids_kernel, dim3(tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, tiles_x, tiles_per_view,
+                           pose, shape_type, prm, cam, fx, fy, cx, cy, W, H, znear, zfar, grid_id, grid_off, grid_dims, grid_data, blk_off,
+                           blk_min, depth, seg);
+    else      // no body is seen through a grid: the analytic renderer's own kernel, the same bits as dss_depth_render
+        hipLaunchKernelGGL(depth_render_kernel, dim3(tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, tiles_x, tiles_per_view, pose,
+                           shape_type, prm, cam, fx, fy, cx, cy, W, H, znear, zfar, depth, seg);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }
 

@@ -25,6 +25,21 @@ int dss_pointcloud_loss(int nseg, int max_seg_len, const int *seg_off, const dou
                         const int *shape_type, const double *prm, double *out, void *workspace, size_t workspace_bytes,
                         void *stream);
 
+/* dss_pointcloud_loss with voxel-grid segments.  grid_id [nseg] (-1: none) points into the pooled table of DssWorld's
+ * convention: grid_off [ngrid] (offset of a grid's samples in grid_data, in doubles), grid_dims [ngrid][3] (>= 2 per axis, x
+ * slowest), grid_data.  Segments of types 0-5 are computed by the same code as in dss_pointcloud_loss (grid_id is not read for
+ * them).  A segment of DSS_SHAPE_GRID with grid_id >= 0 has phi = scale * trilinear(samples) (scale = prm[3]; geom.h's
+ * SHAPE_GRID value) and, as the derivative of phi w.r.t. the body-frame point, DiffGridSDF's rule: the interpolated
+ * central-difference field of the samples, normalised once -- NOT the derivative of the trilinear value.  The chain to position
+ * and raw quaternion is the one of the analytic segments; the three prm outputs of a grid segment are exactly 0.
+ * DSS_SHAPE_IGR, and DSS_SHAPE_GRID with grid_id < 0, give DSS_E_UNSUPPORTED and leave `out` untouched; a grid_id >= ngrid or a
+ * dim < 2 gives DSS_E_BADARG.  Same workspace (dss_pointcloud_loss_workspace_bytes), same two kernels' structure, same 12
+ * outputs, no atomics.  The host reads shape_type, grid_id and grid_dims (and waits for the stream) before it enqueues. */
+int dss_pointcloud_loss_grids(int nseg, int max_seg_len, const int *seg_off, const double *pts, const double *pose,
+                              const int *shape_type, const double *prm, const int *grid_id, int ngrid, const int *grid_off,
+                              const int *grid_dims, const double *grid_data, double *out, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

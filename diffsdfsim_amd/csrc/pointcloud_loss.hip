@@ -3,6 +3,8 @@
 //
 //   dss_pointcloud_loss   per segment s: out[s] = sum over its points inside the body's query cube of
 //                         (phi^2, 1, d phi^2 / d pose[7], d phi^2 / d prm[3])   (pointcloud_point.h)
+//   dss_pointcloud_loss_grids   the same with voxel-grid segments (SHAPE_GRID) from a pooled grid table: a kernel of its own,
+//                         the analytic loops shared
 //
 // One lane per point in a strided loop, 256-thread workgroups, one workgroup per (segment, chunk of a segment) -- a flat
 // grid of nseg * chunks, segment-major; a workgroup covers PC_CHUNK consecutive points of its segment.  Each lane keeps the
@@ -39,33 +41,24 @@ template <int TYPE> __device__ __forceinline__ void pc_accumulate(const double *
     }
 }
 
-__global__ void __launch_bounds__(PC_THREADS) pointcloud_loss_kernel(int max_seg_len, int chunks, const int *__restrict__ seg_off,
-                                                                    const double *__restrict__ pts, const double *__restrict__ pose,
-                                                                    const int *__restrict__ shape_type, const double *__restrict__ prm,
-                                                                    double *__restrict__ partial)
+// the chunk of workgroup blockIdx.x: -> false if it holds nothing of its segment
+__device__ __forceinline__ bool pc_chunk(int max_seg_len, int chunks, const int *__restrict__ seg_off, int &s, int &first, int &lo, int &hi)
 {
-    __shared__ double red[PC_THREADS / WAVE][PC_OUT];
-    const int s = blockIdx.x / chunks, chunk = blockIdx.x - s * chunks, tid = threadIdx.x;
-    const int first = seg_off[s];
+    s = blockIdx.x / chunks;
+    const int chunk = blockIdx.x - s * chunks;
+    first = seg_off[s];
     int len = seg_off[s + 1] - first;
     if (len > max_seg_len) len = max_seg_len;      // the workspace was sized for max_seg_len
-    const int lo = chunk * PC_CHUNK;
-    if (lo >= len) return;                          // (the whole workgroup: nothing of this segment in the chunk)
-    const int hi = lo + PC_CHUNK < len ? lo + PC_CHUNK : len;
-    double acc[PC_OUT];
-#pragma unroll
-    for (int k = 0; k < PC_OUT; ++k) acc[k] = 0.0;
-    const double *P = pts + 3 * (size_t)first, *ps = pose + 7 * (size_t)s, *pr = prm + 4 * (size_t)s;
-    // the segment's shape is the same for the whole workgroup: one loop per primitive, each compiled for its type alone
-    switch (shape_type[s]) {
-    case SHAPE_BOX: pc_accumulate<SHAPE_BOX>(P, lo + tid, hi, ps, pr, acc); break;
-    case SHAPE_SPHERE: pc_accumulate<SHAPE_SPHERE>(P, lo + tid, hi, ps, pr, acc); break;
-    case SHAPE_CYLINDER: pc_accumulate<SHAPE_CYLINDER>(P, lo + tid, hi, ps, pr, acc); break;
-    case SHAPE_BOX_ROUNDED: pc_accumulate<SHAPE_BOX_ROUNDED>(P, lo + tid, hi, ps, pr, acc); break;
-    case SHAPE_BRICK: pc_accumulate<SHAPE_BRICK>(P, lo + tid, hi, ps, pr, acc); break;
-    case SHAPE_BOWL: pc_accumulate<SHAPE_BOWL>(P, lo + tid, hi, ps, pr, acc); break;
-    default: return;      // (neural and grid bodies: the launcher has refused them)
-    }
+    lo = chunk * PC_CHUNK;
+    if (lo >= len) return false;                    // (the whole workgroup: nothing of this segment in the chunk)
+    hi = lo + PC_CHUNK < len ? lo + PC_CHUNK : len;
+    return true;
+}
+
+// the workgroup's partial [12]: wavefront butterflies, then a fixed tree over the four wavefronts
+__device__ __forceinline__ void pc_reduce(const double *acc, double (*red)[PC_OUT], double *__restrict__ partial)
+{
+    const int tid = threadIdx.x;
 #pragma unroll
     for (int k = 0; k < PC_OUT; ++k) {
         const double w = wave_sum(acc[k]);
@@ -74,6 +67,76 @@ __global__ void __launch_bounds__(PC_THREADS) pointcloud_loss_kernel(int max_seg
     __syncthreads();
     if (tid < PC_OUT)
         partial[(size_t)blockIdx.x * PC_OUT + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+// the segment's shape is the same for the whole workgroup: one loop per primitive, each compiled for its type alone
+__device__ __forceinline__ bool pc_analytic(int type, const double *__restrict__ P, int i0, int hi, const double *ps, const double *pr, double *acc)
+{
+    switch (type) {
+    case SHAPE_BOX: pc_accumulate<SHAPE_BOX>(P, i0, hi, ps, pr, acc); break;
+    case SHAPE_SPHERE: pc_accumulate<SHAPE_SPHERE>(P, i0, hi, ps, pr, acc); break;
+    case SHAPE_CYLINDER: pc_accumulate<SHAPE_CYLINDER>(P, i0, hi, ps, pr, acc); break;
+    case SHAPE_BOX_ROUNDED: pc_accumulate<SHAPE_BOX_ROUNDED>(P, i0, hi, ps, pr, acc); break;
+    case SHAPE_BRICK: pc_accumulate<SHAPE_BRICK>(P, i0, hi, ps, pr, acc); break;
+    case SHAPE_BOWL: pc_accumulate<SHAPE_BOWL>(P, i0, hi, ps, pr, acc); break;
+    default: return false;
+    }
+    return true;
+}
+
+__global__ void __launch_bounds__(PC_THREADS) pointcloud_loss_kernel(int max_seg_len, int chunks, const int *__restrict__ seg_off,
+                                                                    const double *__restrict__ pts, const double *__restrict__ pose,
+                                                                    const int *__restrict__ shape_type, const double *__restrict__ prm,
+                                                                    double *__restrict__ partial)
+{
+    __shared__ double red[PC_THREADS / WAVE][PC_OUT];
+    int s, first, lo, hi;
+    if (!pc_chunk(max_seg_len, chunks, seg_off, s, first, lo, hi)) return;
+    double acc[PC_OUT];
+#pragma unroll
+    for (int k = 0; k < PC_OUT; ++k) acc[k] = 0.0;
+    if (!pc_analytic(shape_type[s], pts + 3 * (size_t)first, lo + (int)threadIdx.x, hi, pose + 7 * (size_t)s, prm + 4 * (size_t)s, acc))
+        return;      // (neural and grid bodies: the launcher has refused them)
+    pc_reduce(acc, red, partial);
+}
+
+// The same with voxel-grid segments: type SHAPE_GRID reads the segment's grid from the pooled table.  The value is geom.h's
+// trilinear field and its tangent DiffGridSDF's rule as sdf_unit states it on duals (the once-normalised interpolated
+// central-difference field, not the derivative of the interpolant); the scale is prm[3], a constant, so the three prm
+// tangents stay exactly 0.  The grid pointer and dims go into the segment's Shape, the dual is not widened.
+__global__ void __launch_bounds__(PC_THREADS) pointcloud_loss_grids_kernel(int max_seg_len, int chunks, const int *__restrict__ seg_off,
+                                                                          const double *__restrict__ pts, const double *__restrict__ pose,
+                                                                          const int *__restrict__ shape_type, const double *__restrict__ prm,
+                                                                          const int *__restrict__ grid_id, const int *__restrict__ grid_off,
+                                                                          const int *__restrict__ grid_dims, const double *__restrict__ grid_data,
+                                                                          double *__restrict__ partial)
+{
+    __shared__ double red[PC_THREADS / WAVE][PC_OUT];
+    int s, first, lo, hi;
+    if (!pc_chunk(max_seg_len, chunks, seg_off, s, first, lo, hi)) return;
+    double acc[PC_OUT];
+#pragma unroll
+    for (int k = 0; k < PC_OUT; ++k) acc[k] = 0.0;
+    const double *P = pts + 3 * (size_t)first, *ps = pose + 7 * (size_t)s, *pr = prm + 4 * (size_t)s;
+    const int type = shape_type[s];
+    if (type == SHAPE_GRID) {
+        const int g = grid_id[s];      // (>= 0 and < ngrid: the launcher has checked)
+        PcSegment S;
+        pc_segment(S, ps, SHAPE_GRID, pr);
+        S.shape.grid = grid_data + grid_off[g];
+        for (int i = 0; i < 3; ++i) S.shape.gn[i] = grid_dims[3 * g + i];
+        for (int i = lo + (int)threadIdx.x; i < hi; i += PC_THREADS) {
+            const double x[3] = {P[3 * (size_t)i], P[3 * (size_t)i + 1], P[3 * (size_t)i + 2]};
+            double term[PC_OUT];
+            if (pc_point(S, x, term)) {
+#pragma unroll
+                for (int k = 0; k < PC_OUT; ++k) acc[k] += term[k];
+            }
+        }
+    } else if (!pc_analytic(type, P, lo + (int)threadIdx.x, hi, ps, pr, acc)) {
+        return;      // (neural bodies: the launcher has refused them)
+    }
+    pc_reduce(acc, red, partial);
 }
 
 // out[s][k] = the segment's partials added in index order (zero for an empty segment)
@@ -127,6 +190,48 @@ int dss_pointcloud_loss(int nseg, int max_seg_len, const int *seg_off, const dou
     if (chunks > 0)
         hipLaunchKernelGGL(pointcloud_loss_kernel, dim3(chunks * nseg), dim3(PC_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,
                            shape_type, prm, (double *)workspace);
+    hipLaunchKernelGGL(pointcloud_sum_kernel, dim3((nseg * PC_OUT + PC_THREADS - 1) / PC_THREADS), dim3(PC_THREADS), 0, st, nseg,
+                       max_seg_len, chunks, seg_off, (const double *)workspace, out);
+    return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
+}
+
+int dss_pointcloud_loss_grids(int nseg, int max_seg_len, const int *seg_off, const double *pts, const double *pose, const int *shape_type,
+                              const double *prm, const int *grid_id, int ngrid, const int *grid_off, const int *grid_dims,
+                              const double *grid_data, double *out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (nseg <= 0 || max_seg_len < 0 || !seg_off || !pose || !shape_type || !prm || !out || (max_seg_len > 0 && !pts) || !grid_id || ngrid < 0)
+        return DSS_E_BADARG;
+    if (ngrid > 0 && (!grid_off || !grid_dims || !grid_data)) return DSS_E_BADARG;
+    if ((long long)nseg * pc_chunks(max_seg_len) > 0x7fffffffLL / PC_OUT) return DSS_E_UNSUPPORTED;      // grid.x, int indices
+    const size_t need = dss_pointcloud_loss_workspace_bytes(nseg, max_seg_len);
+    if (need > 0 && (!workspace || workspace_bytes < need)) return DSS_E_WORKSPACE;
+    // shape types, grid ids and the grids' dims decide the status: the host reads them before anything is enqueued
+    hipStream_t st = (hipStream_t)stream;
+#if defined(DSS_EMU)
+    const int *types = shape_type, *ids = grid_id, *dims = grid_dims;      // (the emulator's device memory is the host's)
+#else
+    std::vector<int> host_types(nseg), host_ids(nseg), host_dims(3 * (size_t)ngrid);
+    if (hipMemcpyAsync(host_types.data(), shape_type, sizeof(int) * (size_t)nseg, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(host_ids.data(), grid_id, sizeof(int) * (size_t)nseg, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (ngrid > 0 && hipMemcpyAsync(host_dims.data(), grid_dims, sizeof(int) * 3 * (size_t)ngrid, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return DSS_E_BADARG;
+    const int *types = host_types.data(), *ids = host_ids.data(), *dims = host_dims.data();
+#endif
+    for (int g = 0; g < 3 * ngrid; ++g)
+        if (dims[g] < 2) return DSS_E_BADARG;
+    for (int s = 0; s < nseg; ++s) {
+        if (types[s] == DSS_SHAPE_GRID) {
+            if (ids[s] >= ngrid) return DSS_E_BADARG;
+            if (ids[s] < 0) return DSS_E_UNSUPPORTED;      // a grid body without a grid
+        } else if (types[s] < DSS_SHAPE_BOX || types[s] > DSS_SHAPE_BOWL) {
+            return DSS_E_UNSUPPORTED;      // neural bodies: the network is not in this loss
+        }
+    }
+    const int chunks = pc_chunks(max_seg_len);
+    if (chunks > 0)
+        hipLaunchKernelGGL(pointcloud_loss_grids_kernel, dim3(chunks * nseg), dim3(PC_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,
+                           shape_type, prm, grid_id, grid_off, grid_dims, grid_data, (double *)workspace);
     hipLaunchKernelGGL(pointcloud_sum_kernel, dim3((nseg * PC_OUT + PC_THREADS - 1) / PC_THREADS), dim3(PC_THREADS), 0, st, nseg,
                        max_seg_len, chunks, seg_off, (const double *)workspace, out);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;

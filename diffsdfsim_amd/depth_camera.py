@@ -12,6 +12,10 @@ convention; pixel (row, col) looks along the camera-frame direction ((col + 0.5 
 depth [nview,H,W] float64 is the distance along the optical axis (0: nothing hit within [znear, zfar]), seg [nview,H,W] int32 the
 body hit (-1 none, -2 the trace ran out of iterations).  Boxes, spheres, cylinders and rounded boxes only: any other shape
 raises.  Device tensors only.  Not differentiable: observations are data.
+
+Voxel-grid bodies: `grids=` a grids.GridTable (or a list of [n0,n1,n2] arrays) and `grid_id` [nview,nbody] (-1: none) let bodies of
+shape type 7 (SDFGrid3D) and 6 (a neural SDF3D, seen through the value grid its mesh is extracted from: body_grid) into the
+same images, by dss_depth_render_grids; brick, bowl and a grid or neural body without a grid still raise.
 """
 import numpy as np
 import torch
@@ -42,7 +46,7 @@ def _intrinsics(fx, fy, cx, cy):
     return fx, fy, cx, cy
 
 
-def render_depth(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640, 480), znear=0.1, zfar=100.0):
+def render_depth(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640, 480), znear=0.1, zfar=100.0, grids=None, grid_id=None):
     """-> (depth [nview,H,W] float64, seg [nview,H,W] int32) on the device of `pose`; size = (W, H).  See the module's text."""
     _lib.require_device(pose, prm)
     if pose.dim() != 3 or pose.shape[2] != 7 or pose.dtype != torch.float64 or prm.dtype != torch.float64 or \
@@ -59,10 +63,26 @@ def render_depth(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640, 480
     fx, fy, cx, cy = _intrinsics(fx, fy, cx, cy)
     dev = pose.device
     types = torch.as_tensor(shape_type).to(dev, torch.int32).reshape(nview, nbody).contiguous()
-    fn = _entry("dss_depth_render")
     depth = torch.zeros(nview, H, W, dtype=torch.float64, device=dev)
     seg = torch.full((nview, H, W), -1, dtype=torch.int32, device=dev)
     cam, pose, prm = _camera(cam_pose, dev), pose.detach().contiguous(), prm.detach().contiguous()
+    if grids is not None:
+        from .grids import as_table
+        T = as_table(grids, dev)
+        if grid_id is None:
+            raise ValueError("grids= needs grid_id [nview,nbody] (-1: the body has no grid)")
+        ids = T.ids(grid_id, (nview, nbody), dev)
+        rc = _entry("dss_depth_render_grids")(nview, nbody, _lib.ptr(pose), _lib.ptr(types), _lib.ptr(prm), _lib.ptr(cam), fx, fy, cx, cy, W, H,
+                                              float(znear), float(zfar), _lib.ptr(ids), T.ngrid, _lib.ptr(T.off), _lib.ptr(T.dims),
+                                              _lib.ptr(T.data), _lib.ptr(T.blk_off), _lib.ptr(T.block_min()), _lib.ptr(depth), _lib.ptr(seg),
+                                              _lib.stream_ptr(dev))
+        if rc == -3:
+            raise _lib.HipLibraryError("dss_depth_render_grids: the renderer takes shape types 0-3 and, with a grid_id >= 0, grid and "
+                                       "neural bodies (7, 6); got types %s with grid ids %s" %
+                                       (sorted(set(types.reshape(-1).tolist())), sorted(set(ids.reshape(-1).tolist()))))
+        _lib.check(rc, "dss_depth_render_grids")
+        return depth, seg
+    fn = _entry("dss_depth_render")
     rc = fn(nview, nbody, _lib.ptr(pose), _lib.ptr(types), _lib.ptr(prm), _lib.ptr(cam),
             fx, fy, cx, cy, W, H, float(znear), float(zfar), _lib.ptr(depth), _lib.ptr(seg), _lib.stream_ptr(dev))
     if rc == -3:
@@ -105,10 +125,11 @@ def views_per_chunk(size, max_bytes=256 << 20):
 
 
 def observe(pose, shape_type, prm, body, cam_pose, fx, fy, cx, cy, size=(640, 480), znear=0.1, zfar=100.0, noise=0.0, seed=0,
-            max_bytes=256 << 20):
+            max_bytes=256 << 20, grids=None, grid_id=None):
     """render_depth and observed_points over all views, at most `max_bytes` of depth and segment images at a time (a 640 x 480
     view is 3.7 MB).  noise: the reference's depth_noise_factor, applied between the two kernels as Recorder3D.get_pointcloud
     does, depth += randn * noise * depth^2 (a pixel of depth 0 stays 0), from a generator seeded with `seed` on the device.
+    grids, grid_id [nview,nbody]: as in render_depth.
     -> (pts [N,3], seg_off [nview+1]) as observed_points returns them."""
     nview = pose.shape[0]
     per = views_per_chunk(size, max_bytes)
@@ -116,10 +137,31 @@ def observe(pose, shape_type, prm, body, cam_pose, fx, fy, cx, cy, size=(640, 48
     gen.manual_seed(int(seed))
     types = torch.as_tensor(shape_type).to(pose.device, torch.int32).reshape(nview, -1)
     pts, off = [], [np.zeros(1, np.int64)]
+    if grids is not None:
+        from .grids import as_table
+        grids = as_table(grids, pose.device)      # (once: its block minima are shared by the chunks)
+        grid_id = torch.as_tensor(grid_id).reshape(nview, -1)
     for v0 in range(0, nview, per):
-        depth, seg = render_depth(pose[v0:v0 + per], types[v0:v0 + per], prm[v0:v0 + per], cam_pose, fx, fy, cx, cy, size, znear, zfar)
+        depth, seg = render_depth(pose[v0:v0 + per], types[v0:v0 + per], prm[v0:v0 + per], cam_pose, fx, fy, cx, cy, size, znear, zfar,
+                                  grids, None if grids is None else grid_id[v0:v0 + per])
         if noise > 0:
             depth += torch.randn(depth.shape, dtype=depth.dtype, device=depth.device, generator=gen) * noise * depth ** 2
         p, o = observed_points(depth, seg, body, cam_pose, fx, fy, cx, cy)
         pts.append(p); off.append(o[1:] + off[-1][-1])
     return torch.cat(pts), np.concatenate(off)
+
+
+def body_grid(body):
+    """The grid through which the camera sees a level-set body -> (samples [n0,n1,n2] float64, scale).  SDFGrid3D: its own `sdf`.
+    A neural SDF3D: the network's values on the res^3 lattice its mesh was extracted from (the same lattice and the same
+    igr.igr_values call as meshsdf.igr_mesh), so the camera shows the surface that marching cubes meshed."""
+    from . import igr, meshsdf
+    from .physics3d.bodies import SDF3D, SDFGrid3D
+    if isinstance(body, SDFGrid3D):
+        return body.sdf, float(body.scale.detach())
+    if isinstance(body, SDF3D):
+        dev = body.igr.packed["W0"].device
+        res = int(body.res)
+        lat = body.latent.detach().to(torch.float64).to(dev)
+        return igr.igr_values(meshsdf._grid_cached(res, dev), lat, body.igr.packed).reshape(res, res, res), float(body.scale.detach())
+    raise TypeError("body_grid: an SDFGrid3D or a neural SDF3D, got %s" % type(body).__name__)

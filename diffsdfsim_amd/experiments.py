@@ -369,8 +369,12 @@ def _depth_observations(world_target, cam_pose, noise, every, run_time, seed, bo
         sc = torch.as_tensor(np.asarray(scene, np.int64), device=world_target.device)
         aux = E.arr["shape_aux"] if "shape_aux" in E.arr else torch.zeros_like(E.arr["shape_prm"][..., 0])
         prm = torch.cat([E.arr["shape_prm"], aux[..., None]], 2)[sc]
+        grid_kw = {}
+        if "grid_data" in E.arr:      # the world's spec carries voxel grids: the camera sees those bodies through them
+            from .grids import GridTable
+            grid_kw = dict(grids=GridTable.from_pooled(E.arr["grid_dims"], E.arr["grid_data"]), grid_id=E.arr["grid_id"][sc])
         pts, off = depth_camera.observe(torch.cat(poses), E.arr["shape_type"][sc], prm, body % world_target.nb, cam_pose, noise=noise,
-                                        seed=seed, max_bytes=max_bytes, **CAMERA)
+                                        seed=seed, max_bytes=max_bytes, **grid_kw, **CAMERA)
     return dict(pts=pts, seg_off=off, time=np.asarray(times), scene=np.asarray(scene, np.int64))
 
 

@@ -294,6 +294,7 @@ class SDF3D(Body3D):
         self.sdf_func, self.params = sdf_func, params
         self.latent = get_tensor(params[0])
         self.scale = get_tensor(scale)
+        self.res = int(res)      # (the lattice of the mesh: depth_camera.body_grid shows the camera the same one)
         v, f = meshsdf.igr_mesh(self.latent, net.packed, res=res)
         self.verts_t = v * self.scale.to(v.device)
         self.verts_np = self.verts_t.detach().cpu().numpy()
@@ -363,6 +364,18 @@ class SDFGrid3D(Body3D):
 
     def query_sdfs(self, pts_loc, return_grads=True, return_overlapmask=False):
         return mass_properties.grid_sdf_query(self.sdf, float(self.scale.detach()), pts_loc, return_grads, return_overlapmask)
+
+    def pointcloud_loss(self, pts_world):
+        """Body3D.pointcloud_loss with this body's own grid (dss_pointcloud_loss_grids): differentiable w.r.t. the pose, by the
+        reference's DiffGridSDF rule; the grid and the scale are constants."""
+        from .. import grids, pointcloud
+        pts = mass_properties._dev(pts_world)
+        if getattr(self, "_grid_table", None) is None:      # (the samples go to the device once)
+            self._grid_table = grids.GridTable([self.sdf], pts.device)
+        prm = torch.tensor([[0.0, 0.0, 0.0, self.shape_aux()]], dtype=torch.float64, device=pts.device)
+        s, n = pointcloud.match_pointcloud(pts, [0, pts.shape[0]], self.p.to(torch.float64).to(pts.device)[None],
+                                           torch.tensor([self.shape_type], dtype=torch.int32), prm, grids=self._grid_table, grid_id=[0])
+        return s[0], n[0]
 
     def _get_ang_inertia(self, mass):
         return self._mesh_ang_inertia(mass)

@@ -47,6 +47,9 @@ OPTIONAL_PROTOTYPES = {
     # the depth camera (csrc/depth_camera.h; exported by every product library, diffsdfsim_amd/depth_camera.py raises where not)
     "dss_depth_render": ("i", "iippppddddiiddppp"), "dss_depth_points_count": ("i", "iiiipppp"),
     "dss_depth_points_emit": ("i", "iiiippppddddpp"),
+    # voxel-grid bodies in the loss and in the camera (the same two headers)
+    "dss_pointcloud_loss_grids": ("i", "iippppppipppppzp"), "dss_grid_block_min": ("i", "ippppipp"),
+    "dss_depth_render_grids": ("i", "iippppddddiiddpipppppppp"),
     # recorded clouds (csrc/cloud_select.h; exported by every product library, diffsdfsim_amd/recorded.py raises where not)
     "dss_cloud_select_count": ("i", "iiiipppp"), "dss_cloud_select_emit": ("i", "iiiippppp"),
     "dss_cloud_stats_workspace_bytes": ("z", "ii"), "dss_cloud_stats": ("i", "iippppzp"),
