@@ -17,6 +17,11 @@
         // ncon <= HCAP anyway; a workgroup falls back to the global array beyond its LDS capacity), and the six
         // numbers a contact contributes (normal, p1) are fetched in one batch per round: every dependent global
         // round trip costs a microsecond here.
+#if !DSS_ALL_SHAPES
+        // the mask of kept contacts below holds 32 rounds of the group: a pair with more contacts than that (in clusters that
+        // each stay below HCAP, or bit 2 is raised anyway) is a capacity error of the lean variant like a cluster beyond HCAP
+        if (ncon > 32 * G::BT) { over |= 2; ncon = 32 * G::BT; }
+#endif
         const bool lds_state = ncon <= G::HCAP;
         if (!lds_state && G::BT == 64) return 1;
         auto get_state = [&](int k) -> int { return lds_state ? (int)S.cst[k] : cstate[k]; };
@@ -128,7 +133,7 @@
 #if DSS_ALL_SHAPES
             const int flag = (k < ncon) && (r < 32 ? (int)((keptbits >> r) & 1u) : (cstate[k] == 2));
 #else
-            const int flag = (k < ncon) && ((keptbits >> r) & 1u);     // (the lean variant stops at HCAP contacts per cluster)
+            const int flag = (k < ncon) && ((keptbits >> r) & 1u);     // (the lean variant stops at HCAP contacts per cluster and 32 rounds per pair)
 #endif
             if (!G::any(flag)) continue;
             const int slot = compact_slot(flag, nout, S);

@@ -339,7 +339,7 @@ class BatchEngine:
         ov = self.get("overflow")
         s = int(np.nonzero(ov)[0][0])
         names = [n for b, n in ((1, "max_cand"), (2, "more than 1024 moving Frank-Wolfe candidates -- or, with the lean kernels (spec['full_kernels'] unset/False), "
-                                         "contacts of one normal cluster -- in a body pair"), (4, "max_pc"), (8, "maxc"), (16, "max_sub (tape slots for the backward pass)"),
+                                         "contacts of one normal cluster, or more than 8192 contacts -- in a body pair"), (4, "max_pc"), (8, "maxc"), (16, "max_sub (tape slots for the backward pass)"),
                                         (32, "igr_qcap (query list of the neural narrow phase)"), (64, "igr_rounds"),
                                         (128, "a contact cluster of more than 48 distinct non-coplanar points, whose hull only the full kernel variants take "
                                               "exactly: construct the engine with spec['full_kernels'] = True (World3D(..., full_kernels=True))")) if ov[s] & b]
