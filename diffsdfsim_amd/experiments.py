@@ -48,6 +48,7 @@ system identification  (experiments/system_identification/optim_sysid.py)
     python -m diffsdfsim_amd.experiments primitives --kind box --scenes 8 --iters 50
     python -m diffsdfsim_amd.experiments sysid --goal mass --scenes 8 --iters 20
     python -m diffsdfsim_amd.experiments pointcloud --shape sphere --scenes 8 --iters 20
+    python -m diffsdfsim_amd.experiments pointcloud --shape igr --net bob_spot --scenes 2 --iters 10
     python -m diffsdfsim_amd.experiments recorded --file real_world_data.pkl [--shape cube]      (or --synthetic)
 """
 import argparse
@@ -444,26 +445,37 @@ def _cloud_prm(shape, rad, corner_r):
     return abi.SHAPE_BOX_ROUNDED, torch.stack([2 * rad, 2 * rad, 2 * rad, z + corner_r], 1)
 
 
-def pointcloud_frame_loss(obs, segs, pose, rad, shape, corner_r=0.2, match=None):
+def pointcloud_frame_loss(obs, segs, pose, rad, shape, corner_r=0.2, match=None, packed=None, latent=None, scale=1.0):
     """sum / max(1, count) per scene of the point-cloud loss over the segments `segs` of `obs`, segment i seen from the pose
     pose[i] [7] of scene obs['scene'][segs[i]] with half size rad[scene] (optim_pointcloud.py:198-201, 284-285).  -> [B] on the
-    device.  match: the loss of the segments (default pointcloud.match_pointcloud, the HIP kernel)."""
+    device.  match: the loss of the segments (default pointcloud.match_pointcloud, the HIP kernel).
+    shape='igr': a neural estimate -- `packed` (pack_weights), `latent` [B, L] (one code per scene, differentiable) and `scale`;
+    `rad` is not read."""
     from . import pointcloud
     match = match or pointcloud.match_pointcloud
     dev = obs["pts"].device
-    B = rad.numel()
-    kind, prm = _cloud_prm(shape, rad.to(dev), corner_r)
     sc = torch.as_tensor(obs["scene"][segs], device=dev)
     off = obs["seg_off"]
     idx = np.concatenate([np.arange(off[i], off[i + 1]) for i in segs]) if len(segs) else np.zeros(0, np.int64)
     loc = np.concatenate([[0], np.cumsum([off[i + 1] - off[i] for i in segs])]).astype(np.int64)
-    s, n = match(obs["pts"][torch.as_tensor(idx, device=dev)], loc, pose.to(dev), torch.full((len(segs),), kind, dtype=torch.int32), prm[sc])
+    if shape == "igr":
+        if packed is None or latent is None:
+            raise ValueError("shape='igr' needs packed= and latent= [B, L]")
+        B = latent.shape[0]
+        prm = torch.zeros(len(segs), 4, dtype=torch.float64, device=dev)
+        prm[:, 3] = scale
+        s, n = match(obs["pts"][torch.as_tensor(idx, device=dev)], loc, pose.to(dev), torch.full((len(segs),), abi.SHAPE_IGR, dtype=torch.int32),
+                     prm, igr=packed, latent=latent.to(dev), latent_id=sc)
+    else:
+        B = rad.numel()
+        kind, prm = _cloud_prm(shape, rad.to(dev), corner_r)
+        s, n = match(obs["pts"][torch.as_tensor(idx, device=dev)], loc, pose.to(dev), torch.full((len(segs),), kind, dtype=torch.int32), prm[sc])
     tot = torch.zeros(B, dtype=torch.float64, device=dev).index_add(0, sc, s)
     cnt = torch.zeros(B, dtype=torch.float64, device=dev).index_add(0, sc, n.to(torch.float64))
     return tot / cnt.clamp_min(1.0)
 
 
-def pointcloud_trajectory_loss(traj, obs, rad, shape, corner_r=0.2, body=-1, match=None):
+def pointcloud_trajectory_loss(traj, obs, rad, shape, corner_r=0.2, body=-1, match=None, packed=None, latent=None, scale=1.0):
     """trajectory_loss of optim_pointcloud.py:204-290, its point-cloud part: every valid trajectory entry whose stamp is within
     1e-5 of an observation's time is compared with that observation's points; per scene sum / max(1, count).  -> [B]"""
     t, ok = traj["t"].cpu().numpy(), traj["valid"].cpu().numpy()
@@ -476,7 +488,7 @@ def pointcloud_trajectory_loss(traj, obs, rad, shape, corner_r=0.2, body=-1, mat
     dev = traj["pose"].device
     ent = np.asarray(ent, np.int64).reshape(-1, 2)
     pose = traj["pose"][torch.as_tensor(ent[:, 0], device=dev), torch.as_tensor(ent[:, 1], device=dev), body]
-    return pointcloud_frame_loss(obs, np.asarray(segs, np.int64), pose, rad, shape, corner_r, match)
+    return pointcloud_frame_loss(obs, np.asarray(segs, np.int64), pose, rad, shape, corner_r, match, packed, latent, scale)
 
 
 def fit_pointcloud(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_pose=None, start_pose=None, run_time=1.5, max_iter=200,
@@ -973,6 +985,62 @@ def fit_trajectory_latent(target_latents, start_latents, packed, run_time=1.0, m
     return dict(latent=lat.detach().numpy().copy(), target=np.asarray(target_latents), history=hist)
 
 
+def fit_pointcloud_latent(target_latents, start_latents, packed, target_pose=None, start_pose=None, run_time=1.0, max_iter=100, lr=1e-3,
+                          conv_thresh=1e-5, latent_reg=1e-4, optimizer="Adam", noise=0.0, every=1, detach_2nd_bounce=True,
+                          fit_first_frame=True, fit_trajectory=True, optimize_pose=False, seed=0, log=None, observe="vertices", **scene):
+    """The two stages of fit_pointcloud for a neural body: the latent code [B, L] (and, with optimize_pose, the start pose) is
+    fitted to what the camera records of bounce_world_latent(target_latents) (pointcloud_observations, either `observe` mode).
+      first frame   the loss of observation 0 seen from the start pose, through the network alone (dss_pointcloud_loss_igr),
+      trajectory    bounce_world_latent + run_world_fixed_dt + pointcloud_trajectory_loss: the latent gradient arrives through the
+                    loss and through the stepper (SDF queries, level-set mesh, inertia).
+    Adam, lr 1e-3 and latent_reg 1e-4 as fit_trajectory_latent; loss = point-cloud loss + latent_reg |latent|^2 per scene.
+    Returns dict(latent, pose, target, history: {'frame': [...], 'trajectory': [...]}, observations)."""
+    T = lambda a: torch.as_tensor(np.asarray(a, np.float64))
+    target = T(target_latents)
+    B = target.shape[0]
+    obj_pos = scene.get("obj_pos", (0.0, 5.0, 0.0))
+    ident = torch.tensor([1.0, 0, 0, 0, *obj_pos], dtype=torch.float64).repeat(B, 1)
+    target_pose = ident.clone() if target_pose is None else T(target_pose).reshape(B, 7)
+    with torch.no_grad():
+        wt = bounce_world_latent(target, packed, run_time=run_time, **scene)
+        obs = pointcloud_observations(wt, camera_pose(), noise=noise, every=every, run_time=run_time, seed=seed, observe=observe)
+    lat = T(start_latents).clone().requires_grad_()
+    start_pose = target_pose.clone() if start_pose is None else T(start_pose).reshape(B, 7)
+    rot, pos = start_pose[:, :4].clone().requires_grad_(optimize_pose), start_pose[:, 4:].clone().requires_grad_(optimize_pose)
+    var = [lat] + ([rot, pos] if optimize_pose else [])
+    first = np.nonzero(obs["time"] < 0)[0]
+    hist = {}
+    for stage in [n for n, on in (("frame", fit_first_frame), ("trajectory", fit_trajectory)) if on]:
+        opt = torch.optim.Adam(var, lr=lr) if optimizer == "Adam" else torch.optim.SGD(var, lr=lr)
+        last, h = None, []
+        for e in range(max_iter):
+            opt.zero_grad()
+            pose0 = torch.cat([rot, pos], 1)
+            if stage == "frame":
+                loss = pointcloud_frame_loss(obs, first, pose0[obs["scene"][first]], None, "igr", packed=packed, latent=lat)
+            else:
+                world = bounce_world_latent(lat, packed, run_time=run_time, **scene)
+                traj = run_world_fixed_dt(world, run_time, detach_2nd_bounce=detach_2nd_bounce)
+                loss = pointcloud_trajectory_loss(traj, obs, None, "igr", packed=packed, latent=lat)
+            loss = loss + latent_reg * (lat.to(loss.device) ** 2).sum(dim=1)
+            loss.sum().backward()
+            l = loss.detach().cpu().numpy()
+            h.append(dict(iter=e, loss=l.copy(), latent=lat.detach().numpy().copy(), grad=lat.grad.numpy().copy(), pose=pose0.detach().numpy().copy()))
+            if log:
+                log("[%s] iter %3d  mean loss %.3e  mean |latent - target| %.4f  |grad| %.3e" %
+                    (stage, e, float(l.mean()), float((lat.detach() - target).abs().mean()), float(lat.grad.abs().mean())))
+            if last is not None and np.all(np.abs(last - l) < conv_thresh):
+                break
+            opt.step()
+            if optimize_pose:
+                with torch.no_grad():
+                    rot /= rot.norm(dim=1, keepdim=True)
+            last = l
+        hist[stage] = h
+    return dict(latent=lat.detach().numpy().copy(), pose=torch.cat([rot, pos], 1).detach().numpy().copy(), target=target.numpy(),
+                history=hist, observations=obs)
+
+
 # ---- inertia fitting: a neural-SDF body spun by a torque (optim_shapespace.py) ------------------------------------------------
 def spin_world(latents, torque_dirs, packed, scale=1.0, mass=1.0, res=128, steps=64, device=None, keep_meshes=True):
     """optim_shapespace.py:71-92 for one scene per latent code: a single neural-SDF body (scale 1) whose translation is locked
@@ -1213,7 +1281,8 @@ def export_trajectory(path, pose, vel, **meta):
 def main(argv=None):
     ap = argparse.ArgumentParser(description="batched experiment drivers (trajectory_fitting/optim_sphere, inertia_fitting/optim_shapespace and optim_primitives, system_identification/optim_sysid)")
     ap.add_argument("what", choices=["sphere", "shapespace", "inertia", "primitives", "sysid", "pointcloud", "recorded"])
-    ap.add_argument("--shape", default="sphere", choices=["sphere", "cube"], help="pointcloud, recorded: the fitted body")
+    ap.add_argument("--shape", default="sphere", choices=["sphere", "cube", "igr"],
+                    help="pointcloud, recorded: the fitted body (igr, pointcloud only: a neural body of --net, its latent code is fitted)")
     ap.add_argument("--file", default=None, help="recorded: the recording (real_world_data.pkl, or an .npz with its keys)")
     ap.add_argument("--synthetic", action="store_true", help="recorded: fit recordings made by synthesize_recording instead of --file")
     ap.add_argument("--optimizer", default="GD", choices=["GD", "Adam"])
@@ -1226,7 +1295,7 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--net", default="bob_spot", choices=["bob_spot", "shapenet"],
-                    help="shapespace, sysid, inertia: the network shape (bob_spot: latent 2, 8 x 128; shapenet: latent 4, 8 x 256)")
+                    help="shapespace, sysid, inertia, pointcloud --shape igr: the network shape (bob_spot: latent 2, 8 x 128; shapenet: latent 4, 8 x 256)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     synthetic_default = a.scenes is None
@@ -1242,6 +1311,14 @@ def main(argv=None):
         print(radius_error_table(res))
         if a.out:
             np.savez_compressed(a.out, **{k.replace(" ", "_").replace(",", ""): v["radius"] for k, v in res.items()}, target=target, start=start)
+    elif a.what == "pointcloud" and a.shape == "igr":
+        from . import igr
+        width, nlat = igr.SHAPES[a.net == "shapenet"]
+        packed = igr.pack_weights(*scenes.geometric_init_weights(a.seed, 0.5, width, nlat))
+        tgt, st = 0.1 * r.standard_normal((a.scenes, nlat)), 0.1 * r.standard_normal((a.scenes, nlat))
+        res = fit_pointcloud_latent(tgt, st, packed, run_time=a.run_time, max_iter=a.iters, log=print, observe=a.observe)
+        for stage, h in res["history"].items():
+            print("pointcloud igr [%s]: mean loss %.3e -> %.3e, %d scenes" % (stage, float(h[0]["loss"].mean()), float(h[-1]["loss"].mean()), a.scenes))
     elif a.what == "pointcloud":
         # optim_pointcloud.py:365-402: target half size ~ U(0.5, 1.5), start = target + U(0, 1); target pose = identity at
         # (0,5,0) perturbed by N(0, 0.1) in rotation and position, start pose = target pose perturbed the same way again
@@ -1256,6 +1333,8 @@ def main(argv=None):
               (a.shape, np.abs(st - tgt).mean(), np.abs(res["rad"] - tgt).mean(), np.linalg.norm(sp[:, 4:] - tp[:, 4:], axis=1).mean(),
                np.linalg.norm(res["pose"][:, 4:] - tp[:, 4:], axis=1).mean(), a.scenes))
     elif a.what == "recorded":
+        if a.shape == "igr":
+            ap.error("recorded: --shape sphere or cube")
         if a.synthetic:
             n = 2 if synthetic_default else a.scenes
             recs = synthesize_recording(rad=0.08 + 0.04 * r.random(n), shape=a.shape, noise=1e-4, seed=a.seed)

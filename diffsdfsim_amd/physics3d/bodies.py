@@ -332,6 +332,17 @@ class SDF3D(Body3D):
         out = (sdf,) + ((grad,) if return_grads else ()) + ((mask,) if return_overlapmask else ())
         return out if len(out) > 1 else out[0]
 
+    def pointcloud_loss(self, pts_world):
+        """Body3D.pointcloud_loss through the network itself (dss_pointcloud_loss_igr): differentiable w.r.t. the pose `p` and
+        the latent code, for either network shape; the scale is a constant.  Needs no world."""
+        from .. import pointcloud
+        pts = mass_properties._dev(pts_world)
+        prm = torch.tensor([[0.0, 0.0, 0.0, self.shape_aux()]], dtype=torch.float64, device=pts.device)
+        s, n = pointcloud.match_pointcloud(pts, [0, pts.shape[0]], self.p.to(torch.float64).to(pts.device)[None],
+                                           torch.tensor([self.shape_type], dtype=torch.int32), prm, igr=self.igr,
+                                           latent=self.latent.to(torch.float64).reshape(1, -1).to(pts.device), latent_id=[0])
+        return s[0], n[0]
+
     def _get_ang_inertia(self, mass):
         return self._mesh_ang_inertia(mass)
 

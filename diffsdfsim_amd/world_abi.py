@@ -55,6 +55,8 @@ OPTIONAL_PROTOTYPES = {
     "dss_cloud_stats_workspace_bytes": ("z", "ii"), "dss_cloud_stats": ("i", "iippppzp"),
     # chamfer distance (csrc/chamfer.h; exported by every product library, diffsdfsim_amd/chamfer.py raises where not)
     "dss_chamfer_nn_workspace_bytes": ("z", "iii"), "dss_chamfer_nn": ("i", "iiipppppppzp"), "dss_chamfer_segment_mean": ("i", "ipppp"),
+    # the point-cloud loss of neural bodies (csrc/pointcloud_loss_igr.h; pointcloud._launch_igr raises where a library does not export it)
+    "dss_pointcloud_loss_igr_workspace_bytes": ("z", "iii"), "dss_pointcloud_loss_igr": ("i", "piippppppiippzp"),
     "dss_diag_set_lcp_stamps": ("v", "pp"), "dss_diag_set_np_stamps": ("v", "pp"), "dss_diag_latency": ("v", "iiippppp"),
     "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"],
 }
