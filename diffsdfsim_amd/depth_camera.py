@@ -16,7 +16,15 @@ raises.  Device tensors only.  Not differentiable: observations are data.
 Voxel-grid bodies: `grids=` a grids.GridTable (or a list of [n0,n1,n2] arrays) and `grid_id` [nview,nbody] (-1: none) let bodies of
 shape type 7 (SDFGrid3D) and 6 (a neural SDF3D, seen through the value grid its mesh is extracted from: body_grid) into the
 same images, by dss_depth_render_grids; brick, bowl and a grid or neural body without a grid still raise.
+
+The colour camera (csrc/shade_camera.hip, ABI: csrc/shade_camera.h) shades those images: surface normals, Lambert shading by up to
+four directional lights with hard shadows, the bodies' colours; physics3d.utils.Recorder3D records through it.
+
+    rgb, normal, shade, flags = shade(depth, seg, pose, shape_type, prm, cam_pose, fx, fy, cx, cy, colors, lights)
+    rgb, depth, seg = render_color(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, colors, lights)      # both, in chunks of views
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -119,9 +127,10 @@ def observed_points(depth, seg, body, cam_pose, fx, fy, cx, cy):
     return pts, seg_off
 
 
-def views_per_chunk(size, max_bytes=256 << 20):
-    """How many views `observe` renders at a time: 12 bytes (depth and segment) per pixel within max_bytes, at least one."""
-    return max(1, int(max_bytes) // (12 * int(size[0]) * int(size[1])))
+def views_per_chunk(size, max_bytes=256 << 20, bytes_per_pixel=12):
+    """How many views `observe` renders at a time: 12 bytes (depth and segment) per pixel within max_bytes, at least one.
+    render_color counts the images shade writes as well (bytes_per_pixel)."""
+    return max(1, int(max_bytes) // (int(bytes_per_pixel) * int(size[0]) * int(size[1])))
 
 
 def observe(pose, shape_type, prm, body, cam_pose, fx, fy, cx, cy, size=(640, 480), znear=0.1, zfar=100.0, noise=0.0, seed=0,
@@ -149,6 +158,104 @@ def observe(pose, shape_type, prm, body, cam_pose, fx, fy, cx, cy, size=(640, 48
         p, o = observed_points(depth, seg, body, cam_pose, fx, fy, cx, cy)
         pts.append(p); off.append(o[1:] + off[-1][-1])
     return torch.cat(pts), np.concatenate(off)
+
+
+def _lights(lights, dev):
+    """lights: rows of (direction towards the light [3], intensity) or [nlight,4] -> ([nlight,4] float64 on dev or None, nlight)."""
+    rows = [] if lights is None else [np.concatenate([np.asarray(r[0], np.float64).reshape(3), [float(r[1])]]) if len(r) == 2
+                                      else np.asarray(r, np.float64).reshape(4) for r in
+                                      (lights.detach().cpu().numpy() if torch.is_tensor(lights) else lights)]
+    if len(rows) > 4:
+        raise ValueError("at most 4 lights, got %d" % len(rows))
+    if any(not np.isfinite(r).all() or not np.any(r[:3] != 0.0) for r in rows):
+        raise ValueError("a light is (a finite direction towards it that is not 0, its intensity)")
+    return (torch.as_tensor(np.array(rows, np.float64).reshape(-1, 4)).to(dev).contiguous() if rows else None), len(rows)
+
+
+def shade(depth, seg, pose, shape_type, prm, cam_pose, fx, fy, cx, cy, colors, lights, ambient=0.1, background=(1, 1, 1), shadows=True,
+          shadow_bias=1e-3, zfar=100.0, grids=None, grid_id=None):
+    """Shade the images render_depth returned for the same views (dss_shade_render, csrc/shade_camera.h): the surface normal at
+    every hit, Lambert shading by the lights with hard shadows, the bodies' colours.
+    colors [nview,nbody,3] (or [nbody,3] for every view) in [0, 1]; lights: up to four (direction TOWARDS the light, intensity)
+    in the world frame; ambient the shade of a surface no light reaches; background the colour of a pixel that hit nothing.
+    -> (rgb [nview,H,W,3] uint8, normal [nview,H,W,3] float64 (world frame, 0 where nothing is hit), shade [nview,H,W] float64 =
+    min(1, ambient + sum_k I_k V_k max(0, n . l_k)), flags [nview,H,W] uint8: bit 0 a shadow ray used up its iterations, bit 1
+    the field's gradient vanished and the normal faces the camera) on the device."""
+    _lib.require_device(depth, seg, pose, prm)
+    if depth.dim() != 3 or depth.shape != seg.shape or depth.dtype != torch.float64 or seg.dtype != torch.int32:
+        raise ValueError("depth float64 and seg int32, both [nview,H,W], got %s %s and %s %s" %
+                         (tuple(depth.shape), depth.dtype, tuple(seg.shape), seg.dtype))
+    nview, H, W = depth.shape
+    if pose.dim() != 3 or tuple(pose.shape) != (nview, pose.shape[1], 7) or pose.dtype != torch.float64 or prm.dtype != torch.float64 or \
+            tuple(prm.shape) != (nview, pose.shape[1], 4):
+        raise ValueError("pose [nview,nbody,7] and prm [nview,nbody,4] as float64 for the %d views of depth, got %s and %s" %
+                         (nview, tuple(pose.shape), tuple(prm.shape)))
+    nbody = pose.shape[1]
+    if nview < 1 or H < 1 or W < 1 or nview * H * W > 2 ** 31 - 1 or not 1 <= nbody <= MAX_BODIES:
+        raise ValueError("at least one pixel, nview * H * W < 2^31 and 1 to %d bodies, got %s with %d" % (MAX_BODIES, tuple(depth.shape), nbody))
+    if not shadow_bias > 0.0 or not zfar > 0.0:
+        raise ValueError("shadow_bias > 0 and zfar > 0, got %r, %r" % (shadow_bias, zfar))
+    fx, fy, cx, cy = _intrinsics(fx, fy, cx, cy)
+    dev = depth.device
+    fn = _entry("dss_shade_render")
+    types = torch.as_tensor(shape_type).to(dev, torch.int32).reshape(nview, nbody).contiguous()
+    col = torch.as_tensor(colors, dtype=torch.float64).to(dev)
+    col = (col.expand(nview, nbody, 3) if col.dim() == 2 else col.reshape(nview, nbody, 3)).contiguous()
+    lt, nlight = _lights(lights, dev)
+    bg = (ctypes.c_double * 3)(*[float(b) for b in background])
+    cam, pose, prm = _camera(cam_pose, dev), pose.detach().contiguous(), prm.detach().contiguous()
+    depth, seg = depth.contiguous(), seg.contiguous()
+    rgb = torch.zeros(nview, H, W, 3, dtype=torch.uint8, device=dev)
+    normal = torch.zeros(nview, H, W, 3, dtype=torch.float64, device=dev)
+    shd = torch.zeros(nview, H, W, dtype=torch.float64, device=dev)
+    flags = torch.zeros(nview, H, W, dtype=torch.uint8, device=dev)
+    if grids is not None:
+        from .grids import as_table
+        T = as_table(grids, dev)
+        if grid_id is None:
+            raise ValueError("grids= needs grid_id [nview,nbody] (-1: the body has no grid)")
+        ids = T.ids(grid_id, (nview, nbody), dev)
+        gargs = (_lib.ptr(ids), T.ngrid, _lib.ptr(T.off), _lib.ptr(T.dims), _lib.ptr(T.data), _lib.ptr(T.blk_off), _lib.ptr(T.block_min()))
+    else:
+        gargs = (None, 0, None, None, None, None, None)
+    rc = fn(nview, nbody, _lib.ptr(pose), _lib.ptr(types), _lib.ptr(prm), _lib.ptr(cam), fx, fy, cx, cy, W, H, float(zfar), *gargs,
+            _lib.ptr(depth), _lib.ptr(seg), _lib.ptr(col), nlight, None if lt is None else _lib.ptr(lt), float(ambient),
+            ctypes.cast(bg, ctypes.c_void_p), int(bool(shadows)), float(shadow_bias), _lib.ptr(normal), _lib.ptr(shd), _lib.ptr(rgb),
+            _lib.ptr(flags), _lib.stream_ptr(dev))
+    if rc == -3:
+        raise _lib.HipLibraryError("dss_shade_render: the camera takes shape types 0-3 and, with a grid_id >= 0, grid and neural bodies "
+                                   "(7, 6); got types %s" % sorted(set(types.reshape(-1).tolist())))
+    _lib.check(rc, "dss_shade_render")
+    return rgb, normal, shd, flags
+
+
+# bytes per pixel of a view while render_color works on it: depth 8 + seg 4, and shade's normal 24 + shade 8 + rgb 3 + flags 1
+_COLOR_BYTES = 12 + 36
+
+
+def render_color(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, colors, lights, size=(640, 480), znear=0.1, zfar=100.0, ambient=0.1,
+                 background=(1, 1, 1), shadows=True, shadow_bias=1e-3, grids=None, grid_id=None, max_bytes=256 << 20):
+    """render_depth, then shade, over all views, at most `max_bytes` of images at a time (views_per_chunk with the 36 further
+    bytes per pixel that shade writes).  -> (rgb [nview,H,W,3] uint8, depth [nview,H,W] float64, seg [nview,H,W] int32)."""
+    nview = pose.shape[0]
+    per = views_per_chunk(size, max_bytes, _COLOR_BYTES)
+    types = torch.as_tensor(shape_type).to(pose.device, torch.int32).reshape(nview, -1)
+    col = torch.as_tensor(colors, dtype=torch.float64)
+    if col.dim() == 2:
+        col = col.expand(nview, *col.shape)
+    if grids is not None:
+        from .grids import as_table
+        grids = as_table(grids, pose.device)      # (once: its block minima are shared by the chunks)
+        grid_id = torch.as_tensor(grid_id).reshape(nview, -1)
+    out = []
+    for v0 in range(0, nview, per):
+        sl = slice(v0, v0 + per)
+        gid = None if grids is None else grid_id[sl]
+        depth, seg = render_depth(pose[sl], types[sl], prm[sl], cam_pose, fx, fy, cx, cy, size, znear, zfar, grids, gid)
+        rgb = shade(depth, seg, pose[sl], types[sl], prm[sl], cam_pose, fx, fy, cx, cy, col[sl], lights, ambient, background, shadows,
+                    shadow_bias, zfar, grids, gid)[0]
+        out.append((rgb, depth, seg))
+    return tuple(torch.cat([o[i] for o in out]) for i in range(3))
 
 
 def body_grid(body):

@@ -28,7 +28,10 @@ class Body3D:
     shape_type = None
 
     def __init__(self, pos, vel=(0, 0, 0, 0, 0, 0), mass=1, restitution=Defaults3D.RESTITUTION,
-                 fric_coeff=Defaults3D.FRIC_COEFF, eps=Defaults3D.EPSILON, **_render_kwargs):
+                 fric_coeff=Defaults3D.FRIC_COEFF, eps=Defaults3D.EPSILON, col=(255, 255, 255), **_render_kwargs):
+        # the colour the recorder draws the body in (utils.Recorder3D), 0..255 per channel as in the reference (bodies.py:404, 441);
+        # thickness, smooth and is_transparent belong to pyrender's meshes and are accepted and dropped
+        self.col = tuple(col)
         pos = get_tensor(pos)
         if pos.numel() == 3:
             self.p = torch.cat([pos.new_tensor([1.0, 0, 0, 0]), pos])

@@ -452,9 +452,32 @@ class World3D(BatchWorld3D):
 
 
 def run_world(world, fixed_dt=False, animation_dt=None, run_time=10, print_time=True, scene=None, recorder=None, **_render):
-    """sdf_physics/physics3d/world.py:113-205 without the pyrender viewer (rendering is out of scope)."""
+    """sdf_physics/physics3d/world.py:113-205 without the pyrender viewer.  With a utils.Scene and a recorder, frames are
+    recorded as the reference's render_step does: one before the first step and one after every step by which `animation_dt`
+    (default: the world's dt) has passed since the last frame -- in simulated time, where the reference's viewer counts wall-clock
+    time -- each appended to world.observations as (t, color_img, depth_img, pc, segmentation_mask, camera_poses).  Force and
+    torque arrows (render_forces, ...) are not drawn.  Without a Scene nothing is recorded."""
+    from .utils import Scene
+    if hasattr(world, "worlds") or not isinstance(scene, Scene):
+        scene = None
+    if animation_dt is None:
+        animation_dt = float(world.dt)
+    prev_frame = -animation_dt
+
+    def render_step(prev_frame):
+        if world.t - prev_frame >= animation_dt:
+            prev_frame = world.t
+            scene.bodies = list(world.bodies)
+            if recorder is not None:
+                world.observations.append((world.t, *recorder.record(world.t, {b: b.col for b in world.bodies})))
+        return prev_frame
+
     start = time.time()
+    if scene is not None:
+        prev_frame = render_step(prev_frame)
     while world.t < run_time:
         world.step(fixed_dt=fixed_dt)
+        if scene is not None:
+            prev_frame = render_step(prev_frame)
         if print_time:
             print("\r {} / {} ".format(world.t, time.time() - start), end="")

@@ -50,6 +50,8 @@ OPTIONAL_PROTOTYPES = {
     # voxel-grid bodies in the loss and in the camera (the same two headers)
     "dss_pointcloud_loss_grids": ("i", "iippppppipppppzp"), "dss_grid_block_min": ("i", "ippppipp"),
     "dss_depth_render_grids": ("i", "iippppddddiiddpipppppppp"),
+    # the colour camera: shading of the depth camera's images (csrc/shade_camera.h; depth_camera.shade raises where it is not exported)
+    "dss_shade_render": ("i", "iippppddddiidpippppppppipdpidppppp"),
     # recorded clouds (csrc/cloud_select.h; exported by every product library, diffsdfsim_amd/recorded.py raises where not)
     "dss_cloud_select_count": ("i", "iiiipppp"), "dss_cloud_select_emit": ("i", "iiiippppp"),
     "dss_cloud_stats_workspace_bytes": ("z", "ii"), "dss_cloud_stats": ("i", "iippppzp"),
