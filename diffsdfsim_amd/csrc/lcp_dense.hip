@@ -605,7 +605,8 @@ int dss_lcp_dense_forward(const double *Q, const double *p, const double *G, con
                           double *slack, double *nu, int *iters, int *status, void *workspace,
                           size_t workspace_bytes, void *stream)
 {
-    if (B <= 0 || nz <= 0 || nineq <= 0 || neq < 0) return DSS_E_BADARG;
+    // max_iter < 1: no iterate is ever evaluated, so there is no best one to return (the reference fails on its `best = None`)
+    if (B <= 0 || nz <= 0 || nineq <= 0 || neq < 0 || max_iter < 1) return DSS_E_BADARG;
     if (!Q || !p || !G || !h || !F || !zhat || !lam || !slack || !iters || !status || !workspace) return DSS_E_BADARG;
     if (neq > 0 && (!A || !b || !nu)) return DSS_E_BADARG;
     if (workspace_bytes < dss_lcp_dense_workspace_bytes(B, nz, nineq, neq)) return DSS_E_WORKSPACE;

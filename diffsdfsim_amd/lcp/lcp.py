@@ -120,12 +120,14 @@ def LCPFunction(eps=1e-12, verbose=0, notImprovedLim=3, max_iter=20, solver=1, c
             Ac, bc = (_dev(A), _dev(b)) if neq > 0 else (Qc.new_empty(0), Qc.new_empty(0))
             zhat, lam, slack, nu, iters, status = lcp_dense_forward(
                 Qc, pc, Gc, hc, Ac, bc, Fc, eps, notImprovedLim, max_iter, check_Q_spd)
-            st = int(status.max().item())  # one host sync; the reference syncs per sample (lcp.py:109-113)
-            if st == 1:
+            # one host sync; the reference syncs per sample (lcp.py:109-113).  The statuses of a batch differ, and the
+            # largest code (4, a warning) must not hide an error (1, 2) of another system
+            not_spd, q_singular, inaccurate = torch.stack([(status == c).any() for c in (1, 2, 4)]).tolist()
+            if not_spd:
                 raise RuntimeError('Q is not SPD.')
-            if st == 2:
+            if q_singular:
                 raise RuntimeError(Q_LU_ERR)
-            if st == 4 and verbose >= 0:
+            if inaccurate and verbose >= 0:
                 print(INACC_ERR)
             ctx.lams, ctx.nus, ctx.slacks, ctx.iters = lam, nu, slack, iters
             ctx.save_for_backward(zhat, Q_, p_, G_, h_, A_, b_, F_)

@@ -60,7 +60,7 @@ OPTIONAL_PROTOTYPES = {
     # the point-cloud loss of neural bodies (csrc/pointcloud_loss_igr.h; pointcloud._launch_igr raises where a library does not export it)
     "dss_pointcloud_loss_igr_workspace_bytes": ("z", "iii"), "dss_pointcloud_loss_igr": ("i", "piippppppiippzp"),
     "dss_diag_set_lcp_stamps": ("v", "pp"), "dss_diag_set_np_stamps": ("v", "pp"), "dss_diag_latency": ("v", "iiippppp"),
-    "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"],
+    "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"], "dss_emu_lcp_dense_group_fits": ("i", "iii"),
 }
 _CTYPE = {"p": _P, "i": _I, "d": _D, "z": ctypes.c_size_t, "v": None}
 

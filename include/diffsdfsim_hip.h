@@ -47,6 +47,18 @@ int dss_abi_version(void);
  *     backward: lcp_physics/lcp/lcp.py:156-213
  * Shapes: Q[B,nz,nz] p[B,nz] G[B,nineq,nz] h[B,nineq] A[B,neq,nz] b[B,neq] F[B,nineq,nineq].
  * neq may be 0 (A, b ignored).  Termination tests are applied per system.
+ * The systems of a launch are independent: what is returned for one does not depend on its neighbours.
+ * Per system: status 0 or DSS_LCP_INACCURATE -> zhat, lam, slack, nu hold the iterate with the smallest residual (not the
+ * last one), iters the index of the iteration that stopped (max_iter if none did).  Status DSS_LCP_NOT_SPD (check_spd != 0
+ * only) or DSS_LCP_Q_SINGULAR -> iters = 0, zhat = 0, and lam, slack, nu of that system are NOT written: they keep what
+ * the caller's arrays held.  Nothing is written past row B of any output.
+ * Argument errors (nothing is launched, nothing is written): DSS_E_BADARG for B, nz or nineq < 1, neq < 0, max_iter < 1
+ * (no iterate would ever be evaluated) or a null pointer that the sizes need; DSS_E_WORKSPACE; DSS_E_UNSUPPORTED where
+ * the staged vectors of a system, 8 (12 nz + nineq + 5 neq + 12) bytes, exceed 64 KB (nz = 681 with nineq = 2 is the
+ * largest nz accepted).
+ * Accuracy on ill-scaled Q (measured up to cond(Q) = 1e10): the residual of the returned iterate is
+ * within 4 x the reference elimination's at every size.  For nz, nineq, neq <= 8 the forward uses explicit inverses of Q and
+ * A Q^-1 A^T: with nz = neq and cond(Q) = 1e10 the equality residual |A x - b| alone reaches 2e-9 (reference: 3e-15).
  * ------------------------------------------------------------------------------------ */
 size_t dss_lcp_dense_workspace_bytes(int B, int nz, int nineq, int neq);
 

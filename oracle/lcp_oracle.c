@@ -300,11 +300,13 @@ static double get_step(int n, const double *v, const double *dv)
 
 /* ---- public entry points (one system) ----------------------------------------------- */
 
-int lcp_oracle_forward1(const double *Q, const double *p, const double *G, const double *h,
-                        const double *A, const double *b, const double *F,
-                        int nz, int nineq, int neq, double eps, int not_improved_lim, int max_iter,
-                        int check_spd, double *zhat, double *lam, double *slack, double *nu,
-                        int *iters, double *best_resid)
+/* resid_hist (may be NULL): the residual of every iteration that was evaluated, resid_hist[0 .. min(iters, max_iter - 1)] --
+ * for the tests that have to show a residual tie or which iterate was the best one. */
+int lcp_oracle_forward1_hist(const double *Q, const double *p, const double *G, const double *h,
+                             const double *A, const double *b, const double *F,
+                             int nz, int nineq, int neq, double eps, int not_improved_lim, int max_iter,
+                             int check_spd, double *zhat, double *lam, double *slack, double *nu,
+                             int *iters, double *best_resid, double *resid_hist)
 {
     kkt_t k;
     if (check_spd) {
@@ -347,6 +349,7 @@ int lcp_oracle_forward1(const double *Q, const double *p, const double *G, const
         double sz = 0; for (int i = 0; i < nineq; ++i) sz += s[i] * z[i];
         double mu = fabs(sz / nineq);
         double resid = norm2(nineq, rz) + (neq ? norm2(neq, ry) : 0.0) + norm2(nz, rx) + nineq * mu;
+        if (resid_hist) resid_hist[it] = resid;
         for (int i = 0; i < nineq; ++i) d[i] = z[i] / s[i];
         factor_kkt(&k, d);
         if (!have_best || resid < best) {
@@ -379,6 +382,16 @@ int lcp_oracle_forward1(const double *Q, const double *p, const double *G, const
     if (best_resid) *best_resid = best;
     free(buf); kkt_free(&k);
     return 0;
+}
+
+int lcp_oracle_forward1(const double *Q, const double *p, const double *G, const double *h,
+                        const double *A, const double *b, const double *F,
+                        int nz, int nineq, int neq, double eps, int not_improved_lim, int max_iter,
+                        int check_spd, double *zhat, double *lam, double *slack, double *nu,
+                        int *iters, double *best_resid)
+{
+    return lcp_oracle_forward1_hist(Q, p, G, h, A, b, F, nz, nineq, neq, eps, not_improved_lim, max_iter, check_spd, zhat, lam, slack,
+                                    nu, iters, best_resid, NULL);
 }
 
 /* lcp.py:156-213.  Gradients have the shapes of the inputs; dA/db untouched when neq == 0. */

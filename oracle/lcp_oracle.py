@@ -51,6 +51,27 @@ def forward(Q, p, G, h, A, b, F, eps=1e-12, not_improved_lim=3, max_iter=20, che
     return zhat, lam, slack, nu, iters, status
 
 
+def residual_history(Q, p, G, h, A, b, F, eps=1e-12, not_improved_lim=3, max_iter=20, check_spd=True):
+    """The residuals the solver evaluated, one array per system (iteration 0 first; empty where Q is refused): what a
+    test needs to show a residual tie, or that the iterate returned is older than the last one."""
+    Q = _c(Q); nB, nz = Q.shape[0], Q.shape[1]
+    G = _c(G); nineq = G.shape[1]
+    A = _c(A); neq = A.shape[1] if A.size else 0
+    p, h, F = _c(p), _c(h), _c(F)
+    A = A if neq else np.zeros((nB, 0, nz)); b = _c(b) if neq else np.zeros((nB, 0))
+    out = []
+    for i in range(nB):
+        z, l, s, n = np.zeros(nz), np.zeros(nineq), np.zeros(nineq), np.zeros(neq + 1)
+        it = ctypes.c_int(0); best = ctypes.c_double(0.0); hist = np.full(max(max_iter, 1), np.nan)
+        Ai, bi = (np.ascontiguousarray(A[i]), np.ascontiguousarray(b[i])) if neq else (np.zeros(1), np.zeros(1))
+        rc = lib().lcp_oracle_forward1_hist(
+            _p(Q[i]), _p(p[i]), _p(G[i]), _p(h[i]), _p(Ai), _p(bi), _p(F[i]), ctypes.c_int(nz), ctypes.c_int(nineq),
+            ctypes.c_int(neq), ctypes.c_double(eps), ctypes.c_int(not_improved_lim), ctypes.c_int(max_iter),
+            ctypes.c_int(int(check_spd)), _p(z), _p(l), _p(s), _p(n), ctypes.byref(it), ctypes.byref(best), _p(hist))
+        out.append(hist[: min(it.value + 1, max_iter)] if rc == 0 else hist[:0])
+    return out
+
+
 def backward(Q, G, A, F, zhat, lam, slack, nu, dl_dz):
     Q = _c(Q); nB, nz = Q.shape[0], Q.shape[1]
     G = _c(G); nineq = G.shape[1]

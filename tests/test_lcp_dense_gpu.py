@@ -82,10 +82,23 @@ def test_lcpfunction_autograd_surface():
     assert rel(Qt.grad.cpu().numpy(), want[0]) < 1e-7
     assert rel(Gt.grad.cpu().numpy(), want[2]) < 1e-7
     # un-batched Q and G broadcast over the batch; their grads are batch means (lcp.py:187-208)
-    Q1 = T(Q[0]).requires_grad_()
+    Qb = np.repeat(Q[:1], 3, axis=0)
+    Q1, G1, h1 = T(Q[0]).requires_grad_(), T(G[0]).requires_grad_(), T(h[0]).requires_grad_()
     z2 = LCPFunction(max_iter=10, verbose=-1)(Q1, T(p), T(G), T(h), e, e, T(F))
     z2.sum().backward()
     assert Q1.grad.shape == (6, 6)
+    z2o, l2o, s2o, nu2o, _, _ = O.forward(Qb, p, G, h, np.zeros((3, 0, 6)), np.zeros((3, 0)), F, max_iter=10)
+    want2 = O.backward(Qb, G, np.zeros((3, 0, 6)), F, z2o, l2o, s2o, nu2o, np.ones((3, 6)))
+    assert rel(Q1.grad.cpu().numpy(), want2[0].mean(0)) < 1e-7
+    # the same for an un-batched G and h (p and F keep the batch)
+    Gb, hb = np.repeat(G[:1], 3, axis=0), np.repeat(h[:1], 3, axis=0)
+    z3 = LCPFunction(max_iter=10, verbose=-1)(T(Q), T(p), G1, h1, e, e, T(F))
+    z3.sum().backward()
+    z3o, l3o, s3o, nu3o, _, _ = O.forward(Q, p, Gb, hb, np.zeros((3, 0, 6)), np.zeros((3, 0)), F, max_iter=10)
+    want3 = O.backward(Q, Gb, np.zeros((3, 0, 6)), F, z3o, l3o, s3o, nu3o, np.ones((3, 6)))
+    assert G1.grad.shape == (4, 6) and h1.grad.shape == (4,)
+    assert rel(G1.grad.cpu().numpy(), want3[2].mean(0)) < 1e-7
+    assert rel(h1.grad.cpu().numpy(), want3[3].mean(0)) < 1e-7
 
 
 def test_non_spd_raises_like_reference():
