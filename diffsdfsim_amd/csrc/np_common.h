@@ -13,6 +13,7 @@
 #include "contact_geom.h"
 #include "diag_stamps.h"
 #include "wave_utils.h"
+#include "wrap2d.h"
 
 namespace {
 using namespace dss;
@@ -586,11 +587,11 @@ template <class G, class P_> __device__ int cluster_hull(ScratchT<G> &S, P_ P, i
         for (int k = tid; k < m; k += G::BT) { const double t = P.hp(k, d) - mean[d]; acc += t * t; }
         var[d] = block_sum(acc, S) / (m - 1);
     }
-    const double tolf = 1e-12 * (1.0 + amax);
+    const double tolf = wrap2_tolf(amax);
     // distance tolerance of the 2-D hull: Qhull merges a vertex that clears its neighbours' edge by less than ~6e-15 of the
     // extent (its `_one-merge`); a box that has turned by 4e-15 rad puts its mid-edge contact points 2e-15 off the edge
     // (dropped there), the smallest excursion seen kept is 4e-11
-    const double dtol = 2e-14 * (1.0 + amax), dtol2 = dtol * dtol;
+    const double dtol = wrap2_dtol(amax), dtol2 = dtol * dtol;
     // farthest point B from A = point 0, then C farthest from line AB
     const double A[3] = {P.hp(0, 0), P.hp(0, 1), P.hp(0, 2)};
     double key = -1.0; int ki = -1;
@@ -823,14 +824,11 @@ template <class G, class P_> __device__ int cluster_hull(ScratchT<G> &S, P_ P, i
                 const double lq = qx * qx + qy * qy;
                 if (!(lq > tolf * tolf)) continue;  // the current point or a duplicate of it
                 if (best < 0) { best = k; bx = qx; by = qy; continue; }
-                const double cr = bx * qy - by * qx, lb = bx * bx + by * by;
                 // clockwise of the best so far by more than round-off, or collinear with it and farther.  Measured like
-                // Qhull measures it: the nearer of the two points clears the line through the farther one by more than
-                // a few ulps of the cluster's extent (Qhull merges facets flatter than that and keeps every vertex that
-                // sticks out more: contact points along an edge are collinear to 1e-9 .. 1e-12 only, and whether such a
-                // point survives changes the contact set)
-                const double c2 = cr * cr, t2 = dtol2 * fmax(lb, lq);
-                if ((cr < 0.0 && c2 > t2) || (c2 <= t2 && lq > lb)) { best = k; bx = qx; by = qy; }
+                // Qhull measures it (wrap2d.h, shared with the 2-D SDF contacts): the nearer of the two points clears the
+                // line through the farther one by more than a few ulps of the cluster's extent (contact points along an edge
+                // are collinear to 1e-9 .. 1e-12 only, and whether such a point survives changes the contact set)
+                if (wrap2_better(bx, by, qx, qy, dtol2)) { best = k; bx = qx; by = qy; }
             }
             S.red_i[tid] = best;
             G::sync();

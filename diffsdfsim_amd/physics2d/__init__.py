@@ -3,3 +3,6 @@ contact handler as a kernel pair (`contacts`), and a world of circles and convex
 kernels (`world`; BASELINE configs[0] end to end without the reference)."""
 from .contacts import DiffContactHandler, contacts2d, make_handler, MAXV  # noqa: F401
 from .world import Body, Circle, Defaults, Gravity, Hull, Rect, TotalConstraint, World, run_world  # noqa: F401
+# the reference's 2-D SDF layer (sdf_physics.physics): bodies with an SDF and an outline, and their contact search on the device
+from .sdf_bodies import SDF, SDFBowl, SDFCircle, SDFGrid, SDFRect  # noqa: F401
+from .sdf_contacts import SDFContactHandler, sdf_contacts2d  # noqa: F401

@@ -12,6 +12,8 @@ What is restated, with the reference's semantics:
   step        step / step_dt: solve, move, detect, accept or halve dt (strict_no_penetration) world.py:119-139, 241-379
   Jacobians   Jc, Jf (two directions), mu, E, restitutions                                world.py:402-501
   engine      u = M v + dt f; contact-free: the KKT inverse; else the LCP                  engines.py:31-83
+  SDF bodies  sdf_bodies.py (SDFRect, SDFCircle, SDFBowl, SDFGrid): their pairs go to `dss_sdf2d_contacts_forward`, one launch
+              per detection (sdf_contacts.py)                                              sdf_physics/physics/contacts.py:31-141
 Not restated: joints other than TotalConstraint, the time-of-contact differential (off by default in 2-D), post-stabilisation,
 pygame drawing.  A world holds its pairs in the order (i < j), bodies in list order -- the order the goldens were recorded in
 (oracle/refshim/fake_ode.py)."""
@@ -135,7 +137,9 @@ class TotalConstraint:
 
 class World:
     """`lcp_physics.physics.world.World(bodies, constraints, dt, eps, tol, fric_dirs, strict_no_penetration)` for the bodies
-    above.  `contacts` after a step: list of ((normal, p1, p2, penetration), i1, i2), as the reference keeps it."""
+    above.  `contacts` after a step: list of ((normal, p1, p2, penetration), i1, i2), as the reference keeps it.
+    `sdf_cap` (attribute, 16): the most contacts one pair of SDF bodies may have after thinning; a pair with more raises the
+    capacity error, and setting `world.sdf_cap` higher before the next step lifts it."""
 
     def __init__(self, bodies, constraints=(), dt=Defaults.DT, eps=Defaults.EPSILON, tol=Defaults.TOL, fric_dirs=Defaults.FRIC_DIRS,
                  strict_no_penetration=True, max_iter=10):
@@ -144,6 +148,7 @@ class World:
         self.bodies, self.dt, self.eps, self.tol, self.fric_dirs = list(bodies), dt, eps, tol, fric_dirs
         self.strict_no_pen, self.max_iter = strict_no_penetration, max_iter
         self.t, self.trajectory, self.lcp_calls = 0.0, [], 0
+        self.sdf_cap, self._sdf_grids = 16, None      # contacts per pair of SDF bodies the kernel may return; the grids' pooled table
         nb = len(self.bodies)
         for c in constraints:
             if not isinstance(c, TotalConstraint):
@@ -180,8 +185,38 @@ class World:
         polygon's `last_sat_idx` is state that the reference carries from one pair to the next (contacts.py:124-131, 153-158),
         so a pair that meets a polygon again starts a new launch with the index the earlier pair left."""
         self.contacts = []
+        if any(hasattr(b, "query_sdfs") for b in self.bodies):
+            self._find_contacts_with_sdf()
+            return
+        self._find_analytic(self.pairs)
+
+    def _find_contacts_with_sdf(self):
+        """A world that holds SDF bodies (sdf_bodies.py): their pairs go to the SDF contact kernel, all of a detection in one
+        launch; pairs of circles and polygons go where they always went; a pair of one of each raises, as the reference's
+        handler asserts.  The contacts are kept in pair order (i < j) and, within a pair, in the kernel's order."""
+        from .sdf_contacts import GridTable, pair_inputs, sdf_contacts2d
+        nsdf = lambda pr: sum(hasattr(self.bodies[i], "query_sdfs") for i in pr)      # noqa: E731
+        plain, sdf_pairs = [pr for pr in self.pairs if nsdf(pr) == 0], [pr for pr in self.pairs if nsdf(pr) == 2]
+        if len(plain) + len(sdf_pairs) != len(self.pairs):
+            raise TypeError("a pair of an SDF body and an analytic body: their contact is not defined (the reference asserts)")
+        self._find_analytic(plain)
+        found = self.contacts
+        if sdf_pairs:
+            if self._sdf_grids is None:      # the grids' samples and outlines do not change: pooled once
+                self._sdf_grids = GridTable([b for b in self.bodies if hasattr(b, "sdf")], self._M.device)
+            a = pair_inputs([(self.bodies[i], self.bodies[j]) for i, j in sdf_pairs], self._M.device, grids=self._sdf_grids)
+            out, count, _tag, _tpar = sdf_contacts2d(eps=self.eps, cap=self.sdf_cap, **a)
+            count = count.cpu()
+            for q, (i, j) in enumerate(sdf_pairs):
+                for c in range(int(count[q])):
+                    o = out[q, c]
+                    found.append(((o[0:2], o[2:4], o[4:6], o[6]), i, j))
+        order = {pr: k for k, pr in enumerate(self.pairs)}
+        self.contacts = sorted(found, key=lambda c: order[(c[1], c[2])])
+
+    def _find_analytic(self, pairs):
         group, seen = [], set()
-        for pr in self.pairs:
+        for pr in pairs:
             hulls = {i for i in pr if self.bodies[i].kind == 1}
             if hulls & seen:
                 self._detect(group)

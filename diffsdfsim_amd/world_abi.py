@@ -59,6 +59,8 @@ OPTIONAL_PROTOTYPES = {
     "dss_chamfer_nn_workspace_bytes": ("z", "iii"), "dss_chamfer_nn": ("i", "iiipppppppzp"), "dss_chamfer_segment_mean": ("i", "ipppp"),
     # the point-cloud loss of neural bodies (csrc/pointcloud_loss_igr.h; pointcloud._launch_igr raises where a library does not export it)
     "dss_pointcloud_loss_igr_workspace_bytes": ("z", "iii"), "dss_pointcloud_loss_igr": ("i", "piippppppiippzp"),
+    # contacts of 2-D SDF bodies (csrc/sdf2d_contacts.h; physics2d/sdf_contacts.py raises where a library does not export it)
+    "dss_sdf2d_contacts_forward": ("i", "iippppppdpppppipppp"), "dss_sdf2d_contacts_backward": ("i", "iipppppppppppppp"),
     "dss_diag_set_lcp_stamps": ("v", "pp"), "dss_diag_set_np_stamps": ("v", "pp"), "dss_diag_latency": ("v", "iiippppp"),
     "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"], "dss_emu_lcp_dense_group_fits": ("i", "iii"),
 }
@@ -80,6 +82,16 @@ IGR_NET_FIELDS = IGR_NET_POINTERS + ("width", "latent")      # hidden width and 
 
 class DssIgrNet(ctypes.Structure):
     _fields_ = [(k, _P if k in IGR_NET_POINTERS else _I) for k in IGR_NET_FIELDS]
+
+
+SDF2D_CIRCLE, SDF2D_RECT, SDF2D_BOWL, SDF2D_GRID = 0, 1, 2, 3      # DSS_SDF2D_<kind> (csrc/sdf2d_contacts.h)
+SDF2D_MAXCAND = 256
+SDF2D_OVER_CAP, SDF2D_OVER_CAND, SDF2D_MALFORMED = 1, 2, 4
+SDF2D_GRID_FIELDS = ("dims", "val_off", "vert_off", "edge_off", "edges", "vals", "grads", "verts")
+
+
+class DssSdf2dGrids(ctypes.Structure):
+    _fields_ = [("ngrids", _I)] + [(k, _P) for k in SDF2D_GRID_FIELDS]
 
 
 # (name, kind) kind: 'i' int scalar, 'd' double scalar, 'pd' double*, 'pi' int*, 'pb' uint8*
