@@ -48,11 +48,31 @@ int dss_sdf2d_contacts_forward(int npairs, int cap, const int *kind, const doubl
                                int *tag, double *tpar, int cand_cap, int *ncand, double *cand, int *cand_tag, void *stream);
 /* gout [P][cap][7] (rows >= count ignored), count / tag / tpar as the forward left them -> g_pose [2][P][3], g_prm [2][P][2],
  * g_scale [2][P].  Every kept contact is recomputed on dual numbers at its fixed edge coordinate (to autograd the search is
- * a constant convex combination of the edge's end points); the grids' samples get no gradient. */
+ * a constant convex combination of the edge's end points).  The table is a constant to this call; the gradient with respect to
+ * it is dss_sdf2d_contacts_backward_grids. */
 int dss_sdf2d_contacts_backward(int npairs, int cap, const int *kind, const double *pose, const double *prm, const double *scale,
                                 const int *grid_id, const DssSdf2dGrids *grids, const int *count, const int *tag,
                                 const double *tpar, const double *gout, double *g_pose, double *g_prm, double *g_scale,
                                 void *stream);
+/* The same, and the gradient with respect to the table's three float arrays, taken as three independent inputs (the caller
+ * chains grads and verts back to the samples):
+ *   g_vals [sum n0 n1], g_grads [sum n0 n1][2], g_verts [sum nv][2], pooled like vals, grads and verts.  The call ADDS into
+ *   them: the caller zeroes them.  g_pose, g_prm, g_scale are written, with the bits dss_sdf2d_contacts_backward writes.
+ * For a kept contact rebuilt at its (direction, edge, t), with O the body whose edge it lies on and Q the body queried: if Q is
+ * a grid, the four samples of the cell receive d / d value (the bilinear weight times the scale into phi) and d / d central
+ * difference (through the normalisation; an interpolated gradient that is exactly zero is passed through unnormalised, as the
+ * forward does); if O is a grid, the two end vertices of the edge receive d / d unit vertex, through the scale, the rotation
+ * and the convex combination, including what the moved point changes in the query of Q.
+ * One 64-lane workgroup per pair, 16 table entries per contact in four passes of dual numbers.  Within a pair the
+ * contributions are added in contact order, entry by entry, by one lane; across pairs they meet in double-precision atomic
+ * adds to global memory.  So g_vals, g_grads and g_verts are bit-reproducible only when no grid is shared between pairs of
+ * the launch; with a shared grid two calls agree to round-off.  No allocation.
+ * A pair whose count is outside 0..cap, a grid id or an edge index outside the table contribute nothing.
+ * DSS_E_BADARG: as dss_sdf2d_contacts_backward, or g_vals, g_grads or g_verts null while `grids` holds a grid. */
+int dss_sdf2d_contacts_backward_grids(int npairs, int cap, const int *kind, const double *pose, const double *prm, const double *scale,
+                                      const int *grid_id, const DssSdf2dGrids *grids, const int *count, const int *tag,
+                                      const double *tpar, const double *gout, double *g_pose, double *g_prm, double *g_scale,
+                                      double *g_vals, double *g_grads, double *g_verts, void *stream);
 
 #ifdef __cplusplus
 }

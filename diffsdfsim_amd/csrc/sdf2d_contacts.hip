@@ -45,6 +45,10 @@ template <class T> struct Body {
     const double *vals, *grads, *gverts;
     const int *gedges;
     int n0, n1, nv, ne;
+    // backward with respect to the table (dss_sdf2d_contacts_backward_grids): where the grid starts in the pooled arrays, and
+    // which of its entries carry the tangents of this pass (0 none, 1 the cell's four samples, 2 / 3 the first / second
+    // component of their central differences, 4 the two vertices sv[0], sv[1] of an edge)
+    int val_base, vert_base, lseed, sv[2];
 };
 
 struct Args {
@@ -65,6 +69,7 @@ template <class T> __host__ __device__ inline bool load_body(const Args &A, int 
     b.scale = T(A.scale[o]);
     b.vals = b.grads = b.gverts = nullptr; b.gedges = nullptr;
     b.n0 = b.n1 = b.nv = 0;
+    b.val_base = b.vert_base = b.lseed = 0; b.sv[0] = b.sv[1] = -1;
     if (b.kind == DSS_SDF2D_RECT) b.ne = 4;
     else if (b.kind == DSS_SDF2D_CIRCLE || b.kind == DSS_SDF2D_BOWL) b.ne = 64;
     else if (b.kind == DSS_SDF2D_GRID) {
@@ -76,6 +81,7 @@ template <class T> __host__ __device__ inline bool load_body(const Args &A, int 
         b.grads = A.G.grads + 2 * (size_t)A.G.val_off[g];
         b.gverts = A.G.verts + 2 * (size_t)A.G.vert_off[g];
         b.gedges = A.G.edges + 2 * (size_t)A.G.edge_off[g];
+        b.val_base = A.G.val_off[g]; b.vert_base = A.G.vert_off[g];
         b.nv = A.G.vert_off[g + 1] - A.G.vert_off[g];
         b.ne = A.G.edge_off[g + 1] - A.G.edge_off[g];
         if (b.nv < 0 || b.ne < 0) return false;
@@ -90,6 +96,12 @@ __host__ __device__ inline double linspace_at(double start, double end, int step
     const double step = (end - start) / (double)(steps - 1);
     return i < steps / 2 ? start + step * (double)i : end - step * (double)(steps - 1 - i);
 }
+
+// a table entry as a T, with tangent `slot` set where T carries tangents
+template <class T> struct Seeded { __host__ __device__ static T at(double x, int) { return T(x); } };
+template <int N> struct Seeded<Dual<N>> {
+    __host__ __device__ static Dual<N> at(double x, int slot) { Dual<N> r(x); r.d[slot] = 1.0; return r; }
+};
 
 // vertex i of the outline in world coordinates (get_surface: verts_loc @ R^T + pos)
 template <class T> __host__ __device__ inline void outline_vertex(const Body<T> &B, int i, T *w)
@@ -106,6 +118,9 @@ template <class T> __host__ __device__ inline void outline_vertex(const Body<T> 
         const double a = linspace_at(-M_PI, 0.0, 32, i < 32 ? i : 63 - i);
         const T rr = i < 32 ? B.prm[0] - B.prm[1] : B.prm[0] + B.prm[1];
         l[0] = cos(a) * rr; l[1] = sin(a) * rr + B.prm[0] / 2.0;
+    } else if (B.lseed == 4 && (i == B.sv[0] || i == B.sv[1])) {      // tangents 0, 1 on the edge's first vertex, 2, 3 on its second
+        const int s0 = i == B.sv[0] ? 0 : 2;
+        l[0] = Seeded<T>::at(B.gverts[2 * i], s0) * B.scale; l[1] = Seeded<T>::at(B.gverts[2 * i + 1], s0 + 1) * B.scale;
     } else {
         l[0] = B.gverts[2 * i] * B.scale; l[1] = B.gverts[2 * i + 1] * B.scale;
     }
@@ -120,8 +135,9 @@ template <class T> __host__ __device__ inline bool edge_ends(const Body<T> &B, i
     return i0 >= 0 && i0 < B.nv && i1 >= 0 && i1 < B.nv;
 }
 
-// query_sdfs of one point: value (world units) and unit gradient (world frame)
-template <class T> __host__ __device__ inline void query(const Body<T> &B, const T *pt, T &phi, T *g)
+// query_sdfs of one point: value (world units) and unit gradient (world frame).  corners: where a grid was interpolated, the
+// numbers of the cell's four samples within the grid (left as they are otherwise)
+template <class T> __host__ __device__ inline void query(const Body<T> &B, const T *pt, T &phi, T *g, size_t *corners = nullptr)
 {
     const T dx = pt[0] - B.pos[0], dy = pt[1] - B.pos[1];
     const T lx = dx * B.c + dy * B.s, ly = dx * (-B.s) + dy * B.c;
@@ -176,10 +192,23 @@ template <class T> __host__ __device__ inline void query(const Body<T> &B, const
         const T ux = (double)x1 - ix, vx = ix - (double)x0, uy = (double)y1 - iy, vy = iy - (double)y0;
         const T wa = ux * uy, wb = ux * vy, wc = vx * uy, wd = vx * vy;
         const size_t ia = (size_t)x0 * B.n1 + y0, ib = (size_t)x0 * B.n1 + y1, ic = (size_t)x1 * B.n1 + y0, id = (size_t)x1 * B.n1 + y1;
-        const T v = wa * B.vals[ia] + wb * B.vals[ib] + wc * B.vals[ic] + wd * B.vals[id];
-        T go[2];
-        for (int k = 0; k < 2; ++k)
-            go[k] = wa * B.grads[2 * ia + k] + wb * B.grads[2 * ib + k] + wc * B.grads[2 * ic + k] + wd * B.grads[2 * id + k];
+        if (corners) { corners[0] = ia; corners[1] = ib; corners[2] = ic; corners[3] = id; }
+        T v, go[2];
+        if (B.lseed >= 1 && B.lseed <= 3) {      // the same sums over table entries that carry tangent c at corner c
+            const size_t at[4] = {ia, ib, ic, id};
+            const T w[4] = {wa, wb, wc, wd};
+            T c[4], d[4][2];
+            for (int k = 0; k < 4; ++k) {
+                c[k] = B.lseed == 1 ? Seeded<T>::at(B.vals[at[k]], k) : T(B.vals[at[k]]);
+                for (int j = 0; j < 2; ++j) d[k][j] = B.lseed == 2 + j ? Seeded<T>::at(B.grads[2 * at[k] + j], k) : T(B.grads[2 * at[k] + j]);
+            }
+            v = w[0] * c[0] + w[1] * c[1] + w[2] * c[2] + w[3] * c[3];
+            for (int j = 0; j < 2; ++j) go[j] = w[0] * d[0][j] + w[1] * d[1][j] + w[2] * d[2][j] + w[3] * d[3][j];
+        } else {
+            v = wa * B.vals[ia] + wb * B.vals[ib] + wc * B.vals[ic] + wd * B.vals[id];
+            for (int k = 0; k < 2; ++k)
+                go[k] = wa * B.grads[2 * ia + k] + wb * B.grads[2 * ib + k] + wc * B.grads[2 * ic + k] + wd * B.grads[2 * id + k];
+        }
         const T n = t_sqrt(go[0] * go[0] + go[1] * go[1]);
         if (val(n) != 0.0) { gl[0] = go[0] / n; gl[1] = go[1] / n; }
         else { gl[0] = go[0]; gl[1] = go[1]; }
@@ -363,41 +392,108 @@ __host__ __device__ inline void seed_coord(Body<Dual<NS>> *b, int k, int slot)
     else B.scale.d[slot] = 1.0;
 }
 
+constexpr int NLOCAL = 16;      // table entries one contact reads with a tangent: 4 samples, 8 central differences, 2 x 2 vertex numbers
+
+// The tuple of the kept contact (dir, e, t) of pair p on NS tangents: coordinates k0 .. k0 + NS - 1 of the pair (lpass 0), or
+// table entries (lpass 1: the four samples of Q's cell, 2 / 3: the components of their central differences, 4: the two end
+// vertices of O's edge).  false: nothing to rebuild (a malformed pair or edge; a pass over a table the body does not read).
+// corners: numbers of the cell's samples within Q's grid ((size_t)-1 where none was interpolated); ends: O's two vertices
+__host__ __device__ inline bool rebuild(const Args &A, int p, int dir, int e, double t, int k0, int lpass, Dual<NS> *row, size_t *corners,
+                                        int *ends, int *val_base, int *vert_base)
+{
+    Body<Dual<NS>> b[2];
+    if (!(load_body(A, p, 0, b[0]) & load_body(A, p, 1, b[1]))) return false;
+    if (lpass == 0)
+        for (int s = 0; s < NS; ++s) seed_coord(b, k0 + s, s);
+    finish_body(b[0]);
+    finish_body(b[1]);
+    Body<Dual<NS>> &O = b[dir], &Q = b[1 - dir];
+    int i0, i1;
+    if (e >= O.ne || !edge_ends(O, e, i0, i1)) return false;
+    if (lpass >= 1 && lpass <= 3) {
+        if (Q.kind != DSS_SDF2D_GRID) return false;
+        Q.lseed = lpass;
+    } else if (lpass == 4) {
+        if (O.kind != DSS_SDF2D_GRID) return false;
+        O.lseed = 4; O.sv[0] = i0; O.sv[1] = i1;
+    }
+    Dual<NS> a[2], bb[2], x[2], phi, g[2];
+    outline_vertex(O, i0, a);
+    outline_vertex(O, i1, bb);
+    for (int k = 0; k < 2; ++k) x[k] = a[k] * (1.0 - t) + bb[k] * t;
+    if (corners) corners[0] = corners[1] = corners[2] = corners[3] = (size_t)-1;
+    query(Q, x, phi, g, corners);
+    make_tuple(x, phi, g, dir, b[0].pos, b[1].pos, row);
+    if (ends) { ends[0] = i0; ends[1] = i1; *val_base = Q.val_base; *vert_base = O.vert_base; }
+    return true;
+}
+
+// GRIDS: also the gradient with respect to the table (g_vals, g_grads, g_verts: pooled like the table, zeroed by the caller).
+// Per block of 64 contacts every lane leaves its contact's NLOCAL contributions in LDS and lane 0 adds them to global memory
+// in contact order, entry by entry: a fixed order within the pair; pairs that share a grid meet in the atomic adds.
+template <bool GRIDS>
 __global__ void __launch_bounds__(64)
 sdf2d_backward_kernel(Args A, const int *count, const int *tag, const double *tpar, const double *gout, double *g_pose, double *g_prm,
-                      double *g_scale)
+                      double *g_scale, double *g_vals, double *g_grads, double *g_verts)
 {
     __shared__ double part[64][NCOORD];
+    __shared__ double loc_v[GRIDS ? 64 : 1][NLOCAL];
+    __shared__ long long loc_at[GRIDS ? 64 : 1][NLOCAL];      // array (0 g_vals, 1 g_grads, 2 g_verts) * 2^48 + element, -1: none
     const int p = blockIdx.x, lane = threadIdx.x, cap = A.cap;
     int n = count[p];
     if (n < 0 || n > cap) n = 0;      // (a pair the forward flagged as over its capacity holds no rows)
     double acc[NCOORD];
     for (int k = 0; k < NCOORD; ++k) acc[k] = 0.0;
-    for (int q = lane; q < n; q += 64) {
-        const size_t o = (size_t)p * cap + q;
-        const int dir = tag[2 * o], e = tag[2 * o + 1];
-        const double t = tpar[o];
-        if (dir < 0 || dir > 1 || e < 0) continue;
-        for (int k0 = 0; k0 < NCOORD; k0 += NS) {
-            Body<Dual<NS>> b[2];
-            if (!(load_body(A, p, 0, b[0]) & load_body(A, p, 1, b[1]))) break;
-            for (int s = 0; s < NS; ++s) seed_coord(b, k0 + s, s);
-            finish_body(b[0]);
-            finish_body(b[1]);
-            const Body<Dual<NS>> &O = b[dir], &Q = b[1 - dir];
-            int i0, i1;
-            if (e >= O.ne || !edge_ends(O, e, i0, i1)) break;
-            Dual<NS> a[2], bb[2], x[2], phi, g[2], row[7];
-            outline_vertex(O, i0, a);
-            outline_vertex(O, i1, bb);
-            for (int k = 0; k < 2; ++k) x[k] = a[k] * (1.0 - t) + bb[k] * t;
-            query(Q, x, phi, g);
-            make_tuple(x, phi, g, dir, b[0].pos, b[1].pos, row);
-            for (int s = 0; s < NS; ++s) {
-                double v = 0.0;
-                for (int j = 0; j < 7; ++j) v += gout[o * 7 + j] * row[j].d[s];
-                acc[k0 + s] += v;
+    for (int base = 0; base < n; base += 64) {
+        const int q = base + lane;
+        if constexpr (GRIDS)
+            for (int s = 0; s < NLOCAL; ++s) loc_at[lane][s] = -1;
+        if (q < n) {
+            const size_t o = (size_t)p * cap + q;
+            const int dir = tag[2 * o], e = tag[2 * o + 1];
+            const double t = tpar[o];
+            if (!(dir < 0 || dir > 1 || e < 0)) {
+                Dual<NS> row[7];
+                for (int k0 = 0; k0 < NCOORD; k0 += NS) {
+                    if (!rebuild(A, p, dir, e, t, k0, 0, row, nullptr, nullptr, nullptr, nullptr)) break;
+                    for (int s = 0; s < NS; ++s) {
+                        double v = 0.0;
+                        for (int j = 0; j < 7; ++j) v += gout[o * 7 + j] * row[j].d[s];
+                        acc[k0 + s] += v;
+                    }
+                }
+                if constexpr (GRIDS)
+                    for (int lpass = 1; lpass <= 4; ++lpass) {
+                        size_t corners[4];
+                        int ends[2], vb = 0, tb = 0;
+                        if (!rebuild(A, p, dir, e, t, 0, lpass, row, corners, ends, &vb, &tb)) continue;
+                        if (lpass < 4 && corners[0] == (size_t)-1) continue;      // outside the grid's box: the value is the scale
+                        for (int s = 0; s < NS; ++s) {
+                            double v = 0.0;
+                            for (int j = 0; j < 7; ++j) v += gout[o * 7 + j] * row[j].d[s];
+                            long long at;
+                            if (lpass == 1) at = (long long)vb + (long long)corners[s];
+                            else if (lpass < 4) at = (1ll << 48) + 2 * ((long long)vb + (long long)corners[s]) + (lpass - 2);
+                            else at = (2ll << 48) + 2 * ((long long)tb + ends[s >> 1]) + (s & 1);
+                            loc_v[lane][(lpass - 1) * NS + s] = v;
+                            loc_at[lane][(lpass - 1) * NS + s] = at;
+                        }
+                    }
             }
+        }
+        if constexpr (GRIDS) {
+            __syncthreads();
+            if (lane == 0) {
+                const int m = n - base < 64 ? n - base : 64;
+                for (int l = 0; l < m; ++l)
+                    for (int s = 0; s < NLOCAL; ++s) {
+                        const long long at = loc_at[l][s];
+                        if (at < 0) continue;
+                        double *dst = (at >> 48) == 0 ? g_vals : ((at >> 48) == 1 ? g_grads : g_verts);
+                        atomicAdd(dst + (at & ((1ll << 48) - 1)), loc_v[l][s]);
+                    }
+            }
+            __syncthreads();
         }
     }
     for (int k = 0; k < NCOORD; ++k) part[lane][k] = acc[k];
@@ -451,7 +547,22 @@ extern "C" int dss_sdf2d_contacts_backward(int npairs, int cap, const int *kind,
     if (!make_args(A, npairs, cap, 0, kind, pose, prm, scale, grid_id, grids, 0.0)) return DSS_E_BADARG;
     if (npairs == 0) return DSS_OK;
     if (!count || !tag || !tpar || !gout || !g_pose || !g_prm || !g_scale) return DSS_E_BADARG;
-    hipLaunchKernelGGL(sdf2d_backward_kernel, dim3(npairs), dim3(64), 0, (hipStream_t)stream, A, count, tag, tpar, gout, g_pose, g_prm,
-                       g_scale);
+    hipLaunchKernelGGL(sdf2d_backward_kernel<false>, dim3(npairs), dim3(64), 0, (hipStream_t)stream, A, count, tag, tpar, gout, g_pose, g_prm,
+                       g_scale, (double *)nullptr, (double *)nullptr, (double *)nullptr);
+    return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_BADARG;
+}
+
+extern "C" int dss_sdf2d_contacts_backward_grids(int npairs, int cap, const int *kind, const double *pose, const double *prm,
+                                                 const double *scale, const int *grid_id, const DssSdf2dGrids *grids, const int *count,
+                                                 const int *tag, const double *tpar, const double *gout, double *g_pose, double *g_prm,
+                                                 double *g_scale, double *g_vals, double *g_grads, double *g_verts, void *stream)
+{
+    Args A;
+    if (!make_args(A, npairs, cap, 0, kind, pose, prm, scale, grid_id, grids, 0.0)) return DSS_E_BADARG;
+    if (A.G.ngrids > 0 && (!g_vals || !g_grads || !g_verts)) return DSS_E_BADARG;
+    if (npairs == 0) return DSS_OK;
+    if (!count || !tag || !tpar || !gout || !g_pose || !g_prm || !g_scale) return DSS_E_BADARG;
+    hipLaunchKernelGGL(sdf2d_backward_kernel<true>, dim3(npairs), dim3(64), 0, (hipStream_t)stream, A, count, tag, tpar, gout, g_pose, g_prm,
+                       g_scale, g_vals, g_grads, g_verts);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_BADARG;
 }

@@ -6,3 +6,4 @@ from .world import Body, Circle, Defaults, Gravity, Hull, Rect, TotalConstraint,
 # the reference's 2-D SDF layer (sdf_physics.physics): bodies with an SDF and an outline, and their contact search on the device
 from .sdf_bodies import SDF, SDFBowl, SDFCircle, SDFGrid, SDFRect  # noqa: F401
 from .sdf_contacts import SDFContactHandler, sdf_contacts2d  # noqa: F401
+from .grid_fit import fit_grid  # noqa: F401

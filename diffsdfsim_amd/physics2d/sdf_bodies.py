@@ -15,8 +15,18 @@ Restated with the reference's semantics, quirks included:
             slot, so only the second survives; that is kept
   inertia   rect m (w^2 + h^2) / 12, circle m r^2 / 2, bowl and grid the outline sum of SDF._get_ang_inertia
   scale     rect 1.5 max(dims), circle 2.6666 rad, bowl 2.6666 (r + d), grid as given
-Not restated: pygame drawing, the ODE broad-phase box (the 2-D world here takes all pairs).  Gradients with respect to a grid's
-samples are not built."""
+Not restated: pygame drawing, the ODE broad-phase box (the 2-D world here takes all pairs).
+
+A grid is differentiable in its samples too: `SDFGrid(..., sdf=<tensor that requires grad>)` keeps the graph, so `query_sdfs`,
+`get_surface`, `verts`, the inertia and, through `sdf_contacts` and `World`, a rollout's loss leave `sdf.grad`.
+  query     plain autograd through the interpolation of the samples and of their central differences, as in the reference
+  outline derivative   the reference has none (`marching_squares` ends in `unique(dim=0)`, whose derivative torch does not
+            implement); this build defines it.  The topology (which sides are crossed, the edges, which vertices are merged)
+            is a constant.  A vertex's derivative is that of its interpolation along its own grid side, p0 + mu (p1 - p0)
+            with mu = -v0 / (v1 - v0) of the side's two samples.  A snapped vertex (|v0|, |v1| or |v0 - v1| below 1e-5: it sits
+            on a sample) has zero derivative.  Vertices merged by `unique` are one grid side seen from its two cells, the
+            same two samples, so nothing is summed over duplicates.  The forward values of `unit_verts` stay the bits
+            `marching_squares` produces: the derivative rides on an added f - f.detach()."""
 import math
 
 import torch
@@ -194,11 +204,13 @@ def central_differences(sdf):
     return g
 
 
-def marching_squares(sdf):
+def marching_squares(sdf, sides=False):
     """Outline of the zero level set of the samples sdf [n0, n1] over [-0.5, 0.5]^2 (host, float64): vertices [nv, 2] unique
     and in lexicographic order, edges [ne, 2] in cell order.  Side k of a cell runs from corner k to corner k + 1 of (top
-    left, top right, bottom right, bottom left); a cell's edge joins its crossed sides in ascending order."""
-    s = sdf.detach().to("cpu", torch.float64)
+    left, top right, bottom right, bottom left); a cell's edge joins its crossed sides in ascending order.
+    sides=True: also, per unique vertex, the flat numbers [nv, 2] of the two samples at the ends of its grid side and whether it
+    was snapped [nv] (one of the two values, or their difference, below 1e-5 in magnitude: the vertex sits on a sample)."""
+    s, with_sides = sdf.detach().to("cpu", torch.float64), sides
     n0, n1 = s.shape
     gx = torch.linspace(-0.5, 0.5, n0, dtype=torch.float64)
     gy = torch.linspace(-0.5, 0.5, n1, dtype=torch.float64)
@@ -212,6 +224,9 @@ def marching_squares(sdf):
     crossed = torch.stack([inside[k] != inside[(k + 1) % 4] for k in range(4)], 1)          # [ncell, 4]
     slot = torch.cumsum(crossed.long().reshape(-1), 0).reshape(ncell, 4) - crossed.long()     # vertex number of (cell, side)
     verts = torch.zeros(int(crossed.sum()), 2, dtype=torch.float64)
+    number = torch.arange(n0 * n1).reshape(n0, n1)
+    I = [number[a, b].reshape(-1) for a, b in win]
+    ends, snapped = torch.zeros(len(verts), 2, dtype=torch.long), torch.zeros(len(verts), dtype=torch.bool)
     for k in range(4):
         p0, p1, v0, v1 = P[k], P[(k + 1) % 4], V[k], V[(k + 1) % 4]
         near0, near1, flat = v0.abs() < 1e-5, v1.abs() < 1e-5, (v0 - v1).abs() < 1e-5
@@ -220,6 +235,8 @@ def marching_squares(sdf):
         at = torch.where(near1[:, None], p1, at)
         at = torch.where((~near0 & ~near1 & ~flat)[:, None], p0 + mu[:, None] * (p1 - p0), at)
         verts[slot[crossed[:, k], k]] = at[crossed[:, k]]
+        ends[slot[crossed[:, k], k]] = torch.stack([I[k], I[(k + 1) % 4]], 1)[crossed[:, k]]
+        snapped[slot[crossed[:, k], k]] = (near0 | near1 | flat)[crossed[:, k]]
     edges = []
     for c in torch.nonzero(crossed.any(1)).reshape(-1).tolist():
         sides = torch.nonzero(crossed[c]).reshape(-1).tolist()
@@ -229,7 +246,15 @@ def marching_squares(sdf):
     edges = torch.tensor(edges, dtype=torch.long).reshape(-1, 2)
     verts, inverse = verts.unique(dim=0, return_inverse=True)
     edges = inverse[edges]
-    return verts, edges[edges[:, 0] != edges[:, 1]]
+    edges = edges[edges[:, 0] != edges[:, 1]]
+    if not with_sides:
+        return verts, edges
+    # vertices that `unique` merged lie on one grid side seen from its two cells (the same two samples), or were snapped to
+    # one sample: any of the merged records serves, and a vertex is snapped if one of them is
+    uends = torch.zeros(len(verts), 2, dtype=torch.long)
+    uends[inverse] = ends
+    usnap = torch.zeros(len(verts), dtype=torch.long).index_add_(0, inverse, snapped.long()) > 0
+    return verts, edges, uends, usnap
 
 
 class SDFGrid(SDF):
@@ -238,10 +263,26 @@ class SDFGrid(SDF):
     def __init__(self, pos, scale, sdf, **kw):
         self.sdf = _t(sdf)
         self.sdf_grads = central_differences(self.sdf)
-        self.unit_verts, self.edges = (x.to(self.sdf.device) for x in marching_squares(self.sdf))
+        self.unit_verts, self.edges, self.vert_samples, self.vert_snapped = (x.to(self.sdf.device) for x in marching_squares(self.sdf, sides=True))
+        if self.sdf.requires_grad:
+            self.unit_verts = self.unit_verts + self._outline_tangent()
         self.scale = _t(scale)
         self.verts = self.unit_verts * self.scale
         super().__init__(pos, scale, **kw)
+
+    def _outline_tangent(self):
+        """Zeros [nv, 2] that carry the outline's derivative with respect to the samples (module docstring, "outline
+        derivative"): f - f.detach() with f the interpolation of every vertex that was not snapped along its own grid side."""
+        n0, n1 = self.sdf.shape
+        free = ~self.vert_snapped
+        i0, i1 = self.vert_samples[free, 0], self.vert_samples[free, 1]
+        flat = self.sdf.reshape(-1).to(torch.float64)
+        gx = torch.linspace(-0.5, 0.5, n0, dtype=torch.float64, device=flat.device)
+        gy = torch.linspace(-0.5, 0.5, n1, dtype=torch.float64, device=flat.device)
+        at = lambda i: torch.stack([gx[i // n1], gy[i % n1]], 1)      # noqa: E731
+        p0, p1, v0, v1 = at(i0), at(i1), flat[i0], flat[i1]
+        f = p0 + (-v0 / (v1 - v0))[:, None] * (p1 - p0)
+        return self.unit_verts.new_zeros(self.unit_verts.shape).index_put((free,), (f - f.detach()).to(self.unit_verts.dtype))
 
     def shape_params(self):
         return self.sdf.new_zeros(2)

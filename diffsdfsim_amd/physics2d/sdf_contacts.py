@@ -6,7 +6,13 @@ other body's SDF, in both directions, and thins what it finds by a PCA and a con
 pair; `sdf_contacts2d` is the batched, differentiable operator, `SDFContactHandler` the class for the reference's
 ``World(..., contact_callback=SDFContactHandler)``, and `physics2d.World` sends its pairs of SDF bodies here.
 
-Gradients reach poses, shape parameters and scales of both bodies.  They are NOT built with respect to a grid body's samples.
+Gradients reach poses, shape parameters and scales of both bodies, and a grid body's samples: `GridTable` pools samples,
+central differences and outline vertices without detaching them, ``dss_sdf2d_contacts_backward_grids`` returns the gradient
+with respect to those three arrays as independent inputs (the reference's graph: `sdf`, `sdf_grads`, `verts` are separate
+tensors there), and autograd chains them back to the samples (`sdf_bodies`: the central differences; the outline derivative
+this build defines).  A foreign grid body without `unit_verts` (the reference's own SDFGrid behind this handler) keeps `sdf`
+and `sdf_grads` connected and its outline detached.  Pairs of one launch that share a grid add into its gradient with
+atomics: such gradients agree between two calls to round-off, not to the bit.
 Within a pair the contacts come in candidate order (body 1's edges in order, then body 2's), not in the order Qhull lists hull
 vertices in."""
 import ctypes
@@ -22,7 +28,8 @@ DEFAULT_CAP = 16
 
 class GridTable:
     """The grid bodies of a set of pairs pooled into the arrays of DssSdf2dGrids on one device (the manner of grids.GridTable).
-    `sources`: objects with `sdf` [n0, n1], `sdf_grads` [n0, n1, 2], outline vertices at unit scale and `edges`."""
+    `sources`: objects with `sdf` [n0, n1], `sdf_grads` [n0, n1, 2], outline vertices at unit scale and `edges`.  The float
+    arrays (`tensors["vals" | "grads" | "verts"]`) are torch.cat's of the sources' own tensors and stay on their graph."""
 
     def __init__(self, sources, device):
         self.ids = {}
@@ -31,12 +38,14 @@ class GridTable:
             if id(b) in self.ids:
                 continue
             self.ids[id(b)] = len(dims) // 2
-            sdf = b.sdf.detach()
+            # the three float arrays stay on the graph of the samples.  A body without `unit_verts` (the reference's own
+            # SDFGrid) gives its outline detached: the reference's graph cannot carry that gradient (unique(dim=0))
+            sdf = b.sdf
             unit = b.unit_verts if hasattr(b, "unit_verts") else b.verts.detach() / b.scale.detach()
             dims += [sdf.shape[0], sdf.shape[1]]
             val_off.append(sum(v.numel() for v in vals))
-            vals.append(sdf.reshape(-1)); grads.append(b.sdf_grads.detach().reshape(-1))
-            verts.append(unit.detach().reshape(-1)); edges.append(b.edges.reshape(-1))
+            vals.append(sdf.reshape(-1)); grads.append(b.sdf_grads.reshape(-1))
+            verts.append(unit.reshape(-1)); edges.append(b.edges.reshape(-1))
             vert_off.append(vert_off[-1] + len(unit)); edge_off.append(edge_off[-1] + len(b.edges))
         i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(device)      # noqa: E731
         f64 = lambda v: (torch.cat([x.to("cpu", torch.float64) for x in v]) if v else torch.zeros(0, dtype=torch.float64)).to(device).contiguous()   # noqa: E731
@@ -87,7 +96,19 @@ def _kernels(get_lib, on_device):
         _lib.check(rc, "dss_sdf2d_contacts_backward")
         return g_pose, g_prm, g_scale
 
-    return forward, backward
+    def backward_grids(kind, pose, prm, scale, grid_id, grids, cap, count, tag, tpar, gout):
+        """The same and the gradient with respect to the table's vals, grads and verts (shaped like them)."""
+        P = pose.shape[1]
+        g_pose, g_prm, g_scale = torch.zeros_like(pose), torch.zeros_like(prm), torch.zeros_like(scale)
+        # (one element at least: a table whose grids have no outline is no null argument)
+        g_tab = [torch.zeros(max(grids.tensors[k].numel(), 1), dtype=torch.float64, device=pose.device) for k in ("vals", "grads", "verts")]
+        rc = entry(get_lib(), "dss_sdf2d_contacts_backward_grids")(
+            P, cap, ptr(kind), ptr(pose), ptr(prm), ptr(scale), ptr(grid_id), grids.address(), ptr(count), ptr(tag), ptr(tpar), ptr(gout),
+            ptr(g_pose), ptr(g_prm), ptr(g_scale), ptr(g_tab[0]), ptr(g_tab[1]), ptr(g_tab[2]), stream(pose))
+        _lib.check(rc, "dss_sdf2d_contacts_backward_grids")
+        return (g_pose, g_prm, g_scale) + tuple(g[:grids.tensors[k].numel()] for g, k in zip(g_tab, ("vals", "grads", "verts")))
+
+    return forward, backward, backward_grids
 
 
 DEVICE_KERNELS = _kernels(_lib.lib, True)
@@ -114,8 +135,11 @@ def check_status(status):
 
 
 class _SdfContacts2D(torch.autograd.Function):
+    """vals, grads, verts: the table's three float arrays as differentiable inputs of their own (None without a table); the
+    kernels read them through `grids`, whose struct points at the same memory."""
+
     @staticmethod
-    def forward(ctx, pose, prm, scale, kind, grid_id, grids, eps, cap, cand_cap, kernels):
+    def forward(ctx, pose, prm, scale, vals, grads, verts, kind, grid_id, grids, eps, cap, cand_cap, kernels):
         pose, prm, scale = pose.contiguous(), prm.contiguous(), scale.contiguous()
         out, count, status, tag, tpar, ncand, cand, cand_tag = kernels[0](kind, pose, prm, scale, grid_id, grids, eps, cap, cand_cap)
         ctx.status = status
@@ -129,8 +153,12 @@ class _SdfContacts2D(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout, *_):
         pose, prm, scale, kind, grid_id, count, tag, tpar = ctx.saved_tensors
-        g = ctx.kernels[1](kind, pose, prm, scale, grid_id, ctx.grids, ctx.cap, count, tag, tpar, gout.contiguous())
-        return g + (None,) * 7
+        args = (kind, pose, prm, scale, grid_id, ctx.grids, ctx.cap, count, tag, tpar, gout.contiguous())
+        if ctx.grids is not None and any(ctx.needs_input_grad[3:6]):
+            g = ctx.kernels[2](*args)
+            tab = tuple(x if need else None for x, need in zip(g[3:], ctx.needs_input_grad[3:6]))
+            return g[:3] + tab + (None,) * 7
+        return ctx.kernels[1](*args) + (None,) * 10
 
 
 def sdf_contacts2d(pose, prm, scale, kind, grid_id, eps, grids=None, cap=DEFAULT_CAP, candidates=0, kernels=DEVICE_KERNELS):
@@ -139,8 +167,11 @@ def sdf_contacts2d(pose, prm, scale, kind, grid_id, eps, grids=None, cap=DEFAULT
     Returns out [P, cap, 7] = (normal, p1, p2, penetration) per contact, count [P], tag [P, cap, 2] = (direction, edge),
     tpar [P, cap]; with candidates = n also ncand [P], cand [P, n, 7], cand_tag [P, n, 2], the contacts before thinning.
     A pair with more contacts than `cap`, or more than DSS_SDF2D_MAXCAND before thinning, raises RuntimeError.
-    No gradient is built with respect to a grid's samples."""
-    return _SdfContacts2D.apply(pose, prm, scale, kind, grid_id, grids, float(eps), int(cap), int(candidates), kernels)
+    Where the table's samples, central differences or outline vertices (`grids.tensors`) require grad, the backward pass is
+    ``dss_sdf2d_contacts_backward_grids`` and their gradients flow on to whatever the table was pooled from; where none
+    does, it is ``dss_sdf2d_contacts_backward`` as before."""
+    tab = [grids.tensors[k] for k in ("vals", "grads", "verts")] if grids is not None else [None] * 3
+    return _SdfContacts2D.apply(pose, prm, scale, *tab, kind, grid_id, grids, float(eps), int(cap), int(candidates), kernels)
 
 
 def is_sdf(body):

@@ -202,7 +202,7 @@ class World:
         self._find_analytic(plain)
         found = self.contacts
         if sdf_pairs:
-            if self._sdf_grids is None:      # the grids' samples and outlines do not change: pooled once
+            if self._sdf_grids is None:      # the grids' samples and outlines do not change: pooled once, on the samples' graph
                 self._sdf_grids = GridTable([b for b in self.bodies if hasattr(b, "sdf")], self._M.device)
             a = pair_inputs([(self.bodies[i], self.bodies[j]) for i, j in sdf_pairs], self._M.device, grids=self._sdf_grids)
             out, count, _tag, _tpar = sdf_contacts2d(eps=self.eps, cap=self.sdf_cap, **a)

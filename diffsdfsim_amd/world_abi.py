@@ -61,6 +61,7 @@ OPTIONAL_PROTOTYPES = {
     "dss_pointcloud_loss_igr_workspace_bytes": ("z", "iii"), "dss_pointcloud_loss_igr": ("i", "piippppppiippzp"),
     # contacts of 2-D SDF bodies (csrc/sdf2d_contacts.h; physics2d/sdf_contacts.py raises where a library does not export it)
     "dss_sdf2d_contacts_forward": ("i", "iippppppdpppppipppp"), "dss_sdf2d_contacts_backward": ("i", "iipppppppppppppp"),
+    "dss_sdf2d_contacts_backward_grids": ("i", "iippppppppppppppppp"),
     "dss_diag_set_lcp_stamps": ("v", "pp"), "dss_diag_set_np_stamps": ("v", "pp"), "dss_diag_latency": ("v", "iiippppp"),
     "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"], "dss_emu_lcp_dense_group_fits": ("i", "iii"),
 }
