@@ -425,6 +425,24 @@ template <class T> __host__ __device__ __forceinline__ void box_unit_grad(const 
     normalize(g1, g);
 }
 
+
+// A voxel grid of nn[3] samples over the unit cube [-1, 1]^3, x slowest: the cell that holds the unit-frame point u (index
+// position (u + 1)/2 (n - 1), the cell clamped to [0, n - 2] so that u = 1 lies in the last cell with weight 1) and the point's
+// place w in that cell; the trilinear weight of the cell's corner (dx, dy, dz).  sdf_unit's SHAPE_GRID value and the sample
+// adjoint of the point-cloud loss (pointcloud_loss_grid_adj.hip) both interpolate through these.
+__host__ __device__ inline void grid_cell(const int *nn, const double *u, int *i0, double *w)
+{
+    for (int d = 0; d < 3; ++d) {
+        const double ind = (u[d] + 1.0) * 0.5 * (double)(nn[d] - 1);
+        int c = (int)floor(ind);
+        c = c < 0 ? 0 : (c > nn[d] - 2 ? nn[d] - 2 : c);
+        i0[d] = c; w[d] = ind - (double)c;
+    }
+}
+__host__ __device__ inline double grid_corner_weight(const double *w, int dx, int dy, int dz)
+{
+    return (dx ? w[0] : 1.0 - w[0]) * (dy ? w[1] : 1.0 - w[1]) * (dz ? w[2] : 1.0 - w[2]);
+}
 #endif
 
 // value and (normalised) gradient of the unit-cube SDF at p = pts/scale, parameters prm/scale
@@ -533,21 +551,17 @@ template <class T> __host__ __device__ inline void sdf_unit(const Shape<T> &s, c
         // that normalised gradient (DiffGridSDF.backward, bodies.py:244-257) and the gradient itself carries no graph.
         const int n0 = s.gn[0], n1 = s.gn[1], n2 = s.gn[2];
         const int nn[3] = {n0, n1, n2};
+        const double u[3] = {val(p[0]), val(p[1]), val(p[2])};
         int i0[3];
         double w[3];
-        for (int d = 0; d < 3; ++d) {
-            const double ind = (val(p[d]) + 1.0) * 0.5 * (double)(nn[d] - 1);
-            int c = (int)floor(ind);
-            c = c < 0 ? 0 : (c > nn[d] - 2 ? nn[d] - 2 : c);
-            i0[d] = c; w[d] = ind - (double)c;
-        }
+        grid_cell(nn, u, i0, w);
         const double *Gd = s.grid;
         auto at = [&](int i, int j, int k) { return Gd[((size_t)i * n1 + j) * n2 + k]; };
         double pv = 0.0, gv[3] = {0.0, 0.0, 0.0};
         for (int dx = 0; dx < 2; ++dx)
             for (int dy = 0; dy < 2; ++dy)
                 for (int dz = 0; dz < 2; ++dz) {
-                    const double wt = (dx ? w[0] : 1.0 - w[0]) * (dy ? w[1] : 1.0 - w[1]) * (dz ? w[2] : 1.0 - w[2]);
+                    const double wt = grid_corner_weight(w, dx, dy, dz);
                     const int i = i0[0] + dx, j = i0[1] + dy, k = i0[2] + dz;
                     pv = pv + at(i, j, k) * wt;
                     const double cx = (i == 0 || i == n0 - 1) ? 0.0 : (at(i + 1, j, k) - at(i - 1, j, k)) / 2.0;

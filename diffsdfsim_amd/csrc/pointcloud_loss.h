@@ -40,6 +40,23 @@ int dss_pointcloud_loss_grids(int nseg, int max_seg_len, const int *seg_off, con
                               const int *grid_dims, const double *grid_data, double *out, void *workspace,
                               size_t workspace_bytes, void *stream);
 
+/* The adjoint of dss_pointcloud_loss_grids with respect to the samples (csrc/pointcloud_loss_grid_adj.hip).  The same segments,
+ * points, poses and table; g_sum [nseg] are the upstream weights of the nseg sums.  For every DSS_SHAPE_GRID segment s with
+ * g_sum[s] != 0 and every point of it inside the query cube, with phi = scale * sum_c w_c sample_c over the 8 corners of the
+ * point's (clamped) cell:
+ *   g_data[grid_off[grid_id[s]] + c] += 2 g_sum[s] phi scale w_c
+ * -- the derivative of the trilinear value itself (the value is linear in the samples); the reference has none.  g_data is
+ * pooled like grid_data and ADDED INTO: the caller zeroes it.  Analytic segments add nothing.  The adds are fp64 global atomics:
+ * the order within one sample is the order of arrival, so two calls agree to the rounding of that sample's sum, not in bits.
+ * The scale's gradient is not computed.  Arguments are checked as by dss_pointcloud_loss_grids, with the same statuses
+ * (DSS_E_BADARG: a null pointer, nseg <= 0, ngrid < 0, a grid_id >= ngrid, a dim < 2; DSS_E_UNSUPPORTED: DSS_SHAPE_IGR, or
+ * DSS_SHAPE_GRID with grid_id < 0); a refused call leaves g_data untouched.  The host reads shape_type, grid_id and grid_dims (and
+ * waits for the stream) before it enqueues its one kernel. */
+int dss_pointcloud_loss_grids_adjoint(int nseg, int max_seg_len, const int *seg_off, const double *pts, const double *pose,
+                                      const int *shape_type, const double *prm, const int *grid_id, int ngrid, const int *grid_off,
+                                      const int *grid_dims, const double *grid_data, const double *g_sum, double *g_data,
+                                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

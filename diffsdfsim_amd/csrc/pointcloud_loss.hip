@@ -16,14 +16,13 @@
 #include <vector>
 
 #include "../../include/diffsdfsim_hip.h"
+#include "pointcloud_chunk.h"
 #include "pointcloud_loss.h"
 #include "pointcloud_point.h"
 #include "wave_utils.h"
 
 namespace {
 using namespace dss;
-
-constexpr int PC_THREADS = 256, PC_CHUNK = 2048;
 
 // the strided loop of one lane over its points of the chunk, for a segment whose body is of type TYPE
 template <int TYPE> __device__ __forceinline__ void pc_accumulate(const double *__restrict__ P, int i0, int hi, const double *pose,
@@ -39,20 +38,6 @@ template <int TYPE> __device__ __forceinline__ void pc_accumulate(const double *
             for (int k = 0; k < PC_OUT; ++k) acc[k] += term[k];
         }
     }
-}
-
-// the chunk of workgroup blockIdx.x: -> false if it holds nothing of its segment
-__device__ __forceinline__ bool pc_chunk(int max_seg_len, int chunks, const int *__restrict__ seg_off, int &s, int &first, int &lo, int &hi)
-{
-    s = blockIdx.x / chunks;
-    const int chunk = blockIdx.x - s * chunks;
-    first = seg_off[s];
-    int len = seg_off[s + 1] - first;
-    if (len > max_seg_len) len = max_seg_len;      // the workspace was sized for max_seg_len
-    lo = chunk * PC_CHUNK;
-    if (lo >= len) return false;                    // (the whole workgroup: nothing of this segment in the chunk)
-    hi = lo + PC_CHUNK < len ? lo + PC_CHUNK : len;
-    return true;
 }
 
 // the workgroup's partial [12]: wavefront butterflies, then a fixed tree over the four wavefronts
@@ -153,8 +138,6 @@ __global__ void __launch_bounds__(PC_THREADS) pointcloud_sum_kernel(int nseg, in
     for (int c = 0; c < nch; ++c) sum += partial[((size_t)s * chunks + c) * PC_OUT + k];
     out[t] = sum;
 }
-
-int pc_chunks(int max_seg_len) { return (max_seg_len + PC_CHUNK - 1) / PC_CHUNK; }
 
 }  // namespace
 

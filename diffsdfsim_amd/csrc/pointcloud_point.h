@@ -65,14 +65,23 @@ __host__ __device__ inline void pc_segment(PcSegment &S, const double *pose, int
     make_shape(S.shape, type, prm, prm4[3]);
 }
 
+// the world-frame point x in the segment's body frame: d = x - pos, p = R^T d
+__host__ __device__ inline void pc_body_point(const PcSegment &S, const double *x, double *d, double *p)
+{
+    for (int i = 0; i < 3; ++i) d[i] = x[i] - S.pos[i];
+    const double *R = S.R;
+    for (int i = 0; i < 3; ++i) p[i] = R[i] * d[0] + R[3 + i] * d[1] + R[6 + i] * d[2];
+}
+
 // terms of the world-frame point x; returns `in` (terms are written only for a point inside the query cube)
 __host__ __device__ inline bool pc_point(const PcSegment &S, const double *x, double *term /*[PC_OUT]*/)
 {
-    const double d[3] = {x[0] - S.pos[0], x[1] - S.pos[1], x[2] - S.pos[2]};
+    double d[3], pb[3];
+    pc_body_point(S, x, d, pb);
     const double *R = S.R;
     PcDual p[3];
     for (int i = 0; i < 3; ++i) {
-        p[i] = PcDual(R[i] * d[0] + R[3 + i] * d[1] + R[6 + i] * d[2]);      // R^T d
+        p[i] = PcDual(pb[i]);
         p[i].d[i] = 1.0;
     }
     PcDual phi, unused[3];
@@ -97,6 +106,32 @@ __host__ __device__ inline bool pc_point(const PcSegment &S, const double *x, do
     term[5] = S.two_s * (sk - qk * gn);
     for (int i = 0; i < 3; ++i) term[6 + i] = -(R[3 * i] * g[0] + R[3 * i + 1] * g[1] + R[3 * i + 2] * g[2]);
     for (int i = 0; i < 3; ++i) term[9 + i] = k * phi.d[3 + i];
+    return true;
+}
+
+// The same point of a voxel-grid segment (S.shape.grid and gn set) as the adjoint of the samples needs it
+// (pointcloud_loss_grid_adj.hip): the membership test, the cell i0 and the place w in it, and phi = scale * the trilinear
+// value -- the value pc_point squares, by query_sdf's cube test and division (geom.h's in_cube and div3), grid_cell and
+// grid_corner_weight, which sdf_unit's SHAPE_GRID branch calls too.  The 8-term sum itself stands here a second time: in sdf_unit
+// it shares its loop with the central-difference field, and taking it out of that loop changes the code of every kernel that
+// queries grids (narrow phase, reverse sweep, camera).  tests/emu/check_pointcloud_grid_adj.cpp holds phi^2 here to the bits of
+// pc_point's term[0] on every point it walks, so the two cannot drift apart unnoticed.
+// phi is linear in the samples: d phi / d sample(corner) = scale * grid_corner_weight(w, corner).
+__host__ __device__ inline bool pc_grid_point(const PcSegment &S, const double *x, int *i0, double *w, double &phi)
+{
+    double d[3], pb[3], u[3];
+    pc_body_point(S, x, d, pb);
+    const double sc = val(S.shape.scale);
+    if (!in_cube(pb, sc)) return false;
+    div3(pb, sc, u);
+    grid_cell(S.shape.gn, u, i0, w);
+    const int n1 = S.shape.gn[1], n2 = S.shape.gn[2];
+    double pv = 0.0;
+    for (int dx = 0; dx < 2; ++dx)
+        for (int dy = 0; dy < 2; ++dy)
+            for (int dz = 0; dz < 2; ++dz)
+                pv = pv + S.shape.grid[((size_t)(i0[0] + dx) * n1 + i0[1] + dy) * n2 + i0[2] + dz] * grid_corner_weight(w, dx, dy, dz);
+    phi = pv * sc;
     return true;
 }
 

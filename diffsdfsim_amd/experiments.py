@@ -49,6 +49,7 @@ system identification  (experiments/system_identification/optim_sysid.py)
     python -m diffsdfsim_amd.experiments sysid --goal mass --scenes 8 --iters 20
     python -m diffsdfsim_amd.experiments pointcloud --shape sphere --scenes 8 --iters 20
     python -m diffsdfsim_amd.experiments pointcloud --shape igr --net bob_spot --scenes 2 --iters 10
+    python -m diffsdfsim_amd.experiments pointcloud --shape grid --res 33 --scenes 2 --iters 100
     python -m diffsdfsim_amd.experiments recorded --file real_world_data.pkl [--shape cube]      (or --synthetic)
 """
 import argparse
@@ -561,6 +562,123 @@ def fit_pointcloud(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_p
         hist[stage] = h
     return dict(rad=rad.detach().numpy().copy(), pose=torch.cat([rot, pos], 1).detach().numpy().copy(), target_rad=target_rad.numpy(),
                 target_pose=target_pose.numpy(), history=hist, observations=obs)
+
+
+# ---- a voxel body fitted to what the camera sees (no counterpart in the reference: its grid samples carry no gradient) -----------
+def orbit_camera_poses(extra=2):
+    """The experiment's camera and `extra` more, turned about the world's vertical axis in equal steps (the body stands on that
+    axis, so each of them sees it from another side at the same distance and height)."""
+    out = []
+    for k in range(extra + 1):
+        a = 2.0 * math.pi * k / (extra + 1)
+        Ry = np.array([[math.cos(a), 0, math.sin(a), 0], [0, 1, 0, 0], [-math.sin(a), 0, math.cos(a), 0], [0, 0, 0, 1.0]])
+        out.append(Ry @ camera_pose())
+    return out
+
+
+def _pose_points(v, pose):
+    """Body-frame points v [N,3] (numpy) in the world frame of pose [7] (raw quaternion normalised by 2 / (q.q))."""
+    r_, i, j, k = pose[:4]
+    ts = 2.0 / (pose[:4] ** 2).sum()
+    R = np.array([[1 - ts * (j * j + k * k), ts * (i * j - k * r_), ts * (i * k + j * r_)], [ts * (i * j + k * r_), 1 - ts * (i * i + k * k), ts * (j * k - i * r_)],
+                  [ts * (i * k - j * r_), ts * (j * k + i * r_), 1 - ts * (i * i + j * j)]])
+    return np.asarray(v, np.float64) @ R.T + pose[4:]
+
+
+def eikonal_residual(sdf):
+    """mean (|grad s| - 1)^2 of unit-frame samples sdf [B,n0,n1,n2] (over [-1,1]^3), per grid: forward differences over the
+    cells' edges, each cell's gradient taken at its low corner.  Plain torch; differentiable."""
+    h = [2.0 / (n - 1) for n in sdf.shape[1:]]
+    gx = (sdf[:, 1:, :-1, :-1] - sdf[:, :-1, :-1, :-1]) / h[0]
+    gy = (sdf[:, :-1, 1:, :-1] - sdf[:, :-1, :-1, :-1]) / h[1]
+    gz = (sdf[:, :-1, :-1, 1:] - sdf[:, :-1, :-1, :-1]) / h[2]
+    return ((torch.sqrt(gx * gx + gy * gy + gz * gz + 1e-12) - 1.0) ** 2).mean(dim=(1, 2, 3))
+
+
+def fit_pointcloud_grid(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_pose=None, start_pose=None, res=17, scale=None,
+                        max_iter=100, lr=0.02, eik_reg=1e-2, optimize_pose=False, extra_cameras=2, noise=0.0, max_points=None, corner_r=0.2,
+                        seed=0, log=None, observe="vertices", mesh_res=128, **scene):
+    """The first-frame stage of fit_pointcloud for a voxel body (SDFGrid3D's field: res^3 samples over the cube of half side
+    `scale`, default 1.5 max(target_rad)).  B scenes; scene s has a target sphere or rounded cube of half size target_rad[s] at
+    target_pose[s].  Observations: pointcloud_observations of the start frame (either `observe` mode) from the experiment's camera
+    and `extra_cameras` more around the vertical axis (orbit_camera_poses), at most max_points of each view (a seeded choice);
+    mesh_res: the resolution of a target cube's level-set mesh (bounce_world's `res`).
+    The grids start as the samples of a sphere of radius start_rad[s]; Adam moves the samples (and, with optimize_pose, the pose)
+    down   loss[s] = sum phi^2 / max(1, count) over the scene's views  +  eik_reg * eikonal_residual(samples)[s]
+    where the first term is match_pointcloud on the grids (its gradient w.r.t. the samples: dss_pointcloud_loss_grids_adjoint).
+    The regulariser is needed: sum phi^2 alone is also least for samples that are all zero.
+    There is no trajectory stage -- the stepper has no adjoint for a grid's samples.
+    Returns dict(sdf [B,res,res,res] unit-frame samples, pose, scale, history [dict(iter, loss, data)], loss_start, loss_final,
+    chamfer_start, chamfer_final [B]: chamfer distance (chamfer.py) between the marching-cubes mesh of the grid, in the world frame of
+    the estimate's pose, and the target's mesh in its own; observations)."""
+    from . import meshsdf, pointcloud
+    from .grids import GridTable
+    T = lambda a: torch.as_tensor(np.asarray(a, np.float64))
+    target_rad, start_rad = T(target_rad).reshape(-1), T(start_rad).reshape(-1)
+    B = target_rad.numel()
+    scale = float(1.5 * target_rad.max()) if scale is None else float(scale)
+    ident = torch.tensor([1.0, 0, 0, 0, 0.0, 5.0, 0.0], dtype=torch.float64).repeat(B, 1)
+    target_pose = ident.clone() if target_pose is None else T(target_pose).reshape(B, 7)
+    rng = np.random.default_rng(seed)
+    with torch.no_grad():
+        wt = bounce_world(target_rad, run_time=0.0, shape=shape, corner_r=corner_r, init_pose=target_pose, res=mesh_res, **scene)
+        dev = wt.device
+        tgt_cloud = chamfer_hip.pack([_pose_points(m[0], target_pose[s].numpy()) for s, m in enumerate(wt.body_meshes)], dev)
+        pts, off, scene_of = [], [0], []
+        for cam in orbit_camera_poses(extra_cameras):      # run_time 0: the start frame alone, one segment per scene and view
+            o = pointcloud_observations(wt, cam, noise=noise, run_time=0.0, seed=seed, observe=observe)
+            so = np.asarray(o["seg_off"].cpu() if torch.is_tensor(o["seg_off"]) else o["seg_off"], np.int64)
+            for i in range(len(so) - 1):
+                idx = np.arange(so[i], so[i + 1])
+                if max_points is not None and len(idx) > max_points:
+                    idx = np.sort(rng.choice(idx, max_points, replace=False))
+                pts.append(o["pts"][torch.as_tensor(idx, device=o["pts"].device)].to(dev)); off.append(off[-1] + len(idx)); scene_of.append(int(o["scene"][i]))
+    obs = dict(pts=torch.cat(pts), seg_off=np.asarray(off, np.int64), scene=np.asarray(scene_of, np.int64))
+    sc = torch.as_tensor(obs["scene"], device=dev)
+    g = torch.linspace(-1.0, 1.0, res, dtype=torch.float64)
+    norm = torch.stack(torch.meshgrid(g, g, g, indexing="ij"), 3).norm(dim=3)
+    sdf = (norm[None] - (start_rad / scale)[:, None, None, None]).to(dev).requires_grad_()
+    start_pose = target_pose.clone() if start_pose is None else T(start_pose).reshape(B, 7)
+    rot, pos = start_pose[:, :4].clone().requires_grad_(optimize_pose), start_pose[:, 4:].clone().requires_grad_(optimize_pose)
+    opt = torch.optim.Adam([sdf] + ([rot, pos] if optimize_pose else []), lr=lr)
+    types = torch.full((len(scene_of),), abi.SHAPE_GRID, dtype=torch.int32)
+    prm = torch.zeros(len(scene_of), 4, dtype=torch.float64, device=dev)
+    prm[:, 3] = scale
+
+    def losses():
+        pose0 = torch.cat([rot, pos], 1).to(dev)
+        s, n = pointcloud.match_pointcloud(obs["pts"], obs["seg_off"], pose0[sc], types, prm, grids=GridTable(list(sdf), dev), grid_id=sc)
+        tot = torch.zeros(B, dtype=torch.float64, device=dev).index_add(0, sc, s)
+        cnt = torch.zeros(B, dtype=torch.float64, device=dev).index_add(0, sc, n)
+        data = tot / cnt.clamp_min(1.0)
+        return data + eik_reg * eikonal_residual(sdf), data
+
+    def chamfer_now():
+        with torch.no_grad():
+            pose0 = torch.cat([rot, pos], 1).detach().numpy()
+            verts = []
+            for s in range(B):
+                v, _ = meshsdf.marching_cubes(sdf[s].detach(), 0.0)
+                verts.append(_pose_points((v.cpu().numpy() / (res - 1) * 2.0 - 1.0) * scale, pose0[s]))
+            return _chamfer_series(verts, tgt_cloud)
+
+    chamfer_start, hist = chamfer_now(), []
+    for e in range(max_iter + 1):      # (the last pass only evaluates)
+        opt.zero_grad()
+        loss, data = losses()
+        hist.append(dict(iter=e, loss=loss.detach().cpu().numpy().copy(), data=data.detach().cpu().numpy().copy()))
+        if log:
+            log("[grid] iter %3d  mean loss %.3e  (points %.3e)" % (e, float(hist[-1]["loss"].mean()), float(hist[-1]["data"].mean())))
+        if e == max_iter:
+            break
+        loss.sum().backward()
+        opt.step()
+        if optimize_pose:
+            with torch.no_grad():
+                rot /= rot.norm(dim=1, keepdim=True)
+    return dict(sdf=sdf.detach().cpu().numpy().copy(), pose=torch.cat([rot, pos], 1).detach().numpy().copy(), scale=scale, history=hist,
+                loss_start=hist[0]["loss"], loss_final=hist[-1]["loss"], chamfer_start=chamfer_start, chamfer_final=chamfer_now(),
+                target_rad=target_rad.numpy(), target_pose=target_pose.numpy(), observations=obs)
 
 
 # ---- trajectory fitting to recorded RGB-D sequences (trajectory_fitting/optim_pointcloud_real.py) ----------------------------
@@ -1281,8 +1399,10 @@ def export_trajectory(path, pose, vel, **meta):
 def main(argv=None):
     ap = argparse.ArgumentParser(description="batched experiment drivers (trajectory_fitting/optim_sphere, inertia_fitting/optim_shapespace and optim_primitives, system_identification/optim_sysid)")
     ap.add_argument("what", choices=["sphere", "shapespace", "inertia", "primitives", "sysid", "pointcloud", "recorded"])
-    ap.add_argument("--shape", default="sphere", choices=["sphere", "cube", "igr"],
-                    help="pointcloud, recorded: the fitted body (igr, pointcloud only: a neural body of --net, its latent code is fitted)")
+    ap.add_argument("--shape", default="sphere", choices=["sphere", "cube", "igr", "grid"],
+                    help="pointcloud, recorded: the fitted body (pointcloud only: igr, a neural body of --net whose latent code is fitted; "
+                         "grid, a voxel body of --res samples per axis whose samples are fitted to a sphere seen from three sides)")
+    ap.add_argument("--res", type=int, default=33, help="pointcloud --shape grid: samples per axis of the voxel body")
     ap.add_argument("--file", default=None, help="recorded: the recording (real_world_data.pkl, or an .npz with its keys)")
     ap.add_argument("--synthetic", action="store_true", help="recorded: fit recordings made by synthesize_recording instead of --file")
     ap.add_argument("--optimizer", default="GD", choices=["GD", "Adam"])
@@ -1319,6 +1439,12 @@ def main(argv=None):
         res = fit_pointcloud_latent(tgt, st, packed, run_time=a.run_time, max_iter=a.iters, log=print, observe=a.observe)
         for stage, h in res["history"].items():
             print("pointcloud igr [%s]: mean loss %.3e -> %.3e, %d scenes" % (stage, float(h[0]["loss"].mean()), float(h[-1]["loss"].mean()), a.scenes))
+    elif a.what == "pointcloud" and a.shape == "grid":
+        tgt = 0.5 + r.random(a.scenes); st = tgt + 0.1 + 0.4 * r.random(a.scenes)
+        res = fit_pointcloud_grid("sphere", tgt, st, res=a.res, max_iter=a.iters, log=print, observe=a.observe)
+        for s in range(a.scenes):
+            print("pointcloud grid scene %d: loss %.3e -> %.3e, chamfer %.3e -> %.3e" %
+                  (s, res["loss_start"][s], res["loss_final"][s], res["chamfer_start"][s], res["chamfer_final"][s]))
     elif a.what == "pointcloud":
         # optim_pointcloud.py:365-402: target half size ~ U(0.5, 1.5), start = target + U(0, 1); target pose = identity at
         # (0,5,0) perturbed by N(0, 0.1) in rotation and position, start pose = target pose perturbed the same way again
@@ -1333,7 +1459,7 @@ def main(argv=None):
               (a.shape, np.abs(st - tgt).mean(), np.abs(res["rad"] - tgt).mean(), np.linalg.norm(sp[:, 4:] - tp[:, 4:], axis=1).mean(),
                np.linalg.norm(res["pose"][:, 4:] - tp[:, 4:], axis=1).mean(), a.scenes))
     elif a.what == "recorded":
-        if a.shape == "igr":
+        if a.shape in ("igr", "grid"):
             ap.error("recorded: --shape sphere or cube")
         if a.synthetic:
             n = 2 if synthetic_default else a.scenes

@@ -6,6 +6,10 @@
 The layout is the stepper's (DssWorld.grid_off / grid_dims / grid_data): `off` [ngrid] int32 offsets into `data`, `dims`
 [ngrid,3] int32, `data` the samples one grid after the other.  The camera also wants the least sample over every block of
 BLOCK cells per axis (dss_grid_block_min); `block_min()` computes them on first use and keeps them.
+
+A table made of tensors of which at least one requires grad keeps the graph in `data` (the grids concatenated, undetached):
+match_pointcloud then returns a loss that is differentiable w.r.t. those grids' samples.  Such a table holds the samples'
+values of the moment it was made; after an optimiser's step make a new one.  Every other table is detached, as before.
 """
 import numpy as np
 import torch
@@ -34,7 +38,12 @@ class GridTable:
         dims = np.array(self.shapes, np.int32)
         self.off = torch.as_tensor(np.cumsum([0] + sizes[:-1]).astype(np.int32)).to(dev)
         self.dims = torch.as_tensor(dims).to(dev)
-        self.data = torch.cat([g.detach().to(dev).reshape(-1) for g in gs]).contiguous()
+        if any(g.requires_grad for g in gs):
+            # a grid that is being fitted: `data` keeps the graph to the grids it pools (match_pointcloud differentiates the loss
+            # w.r.t. it, dss_pointcloud_loss_grids_adjoint); everything else reads its values
+            self.data = torch.cat([g.to(dev).reshape(-1) for g in gs]).contiguous()
+        else:
+            self.data = torch.cat([g.detach().to(dev).reshape(-1) for g in gs]).contiguous()
         nblk = block_counts(dims)
         self.nblk = int(nblk.sum())
         self.blk_off = torch.as_tensor(np.concatenate([[0], np.cumsum(nblk)[:-1]]).astype(np.int32)).to(dev)
@@ -58,7 +67,7 @@ class GridTable:
             if not hasattr(L, "dss_grid_block_min"):
                 raise _lib.HipLibraryError("libdiffsdfsim_hip.so does not export dss_grid_block_min: rebuild it (python __graft_entry__.py build)")
             out = torch.empty(self.nblk, dtype=torch.float64, device=self.device)
-            _lib.check(L.dss_grid_block_min(self.ngrid, _lib.ptr(self.off), _lib.ptr(self.dims), _lib.ptr(self.data), _lib.ptr(self.blk_off),
+            _lib.check(L.dss_grid_block_min(self.ngrid, _lib.ptr(self.off), _lib.ptr(self.dims), _lib.ptr(self.data.detach()), _lib.ptr(self.blk_off),
                                             self.nblk, _lib.ptr(out), _lib.stream_ptr(self.device)), "dss_grid_block_min")
             self._blk_min = out
         return self._blk_min

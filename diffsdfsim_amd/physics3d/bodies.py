@@ -361,7 +361,7 @@ class SDFGrid3D(Body3D):
         self.scale = get_tensor(scale)
         self.sdf = torch.as_tensor(sdf, dtype=torch.float64)
         res = self.sdf.shape[0]
-        v, f = meshsdf.marching_cubes(self.sdf, 0.0)
+        v, f = meshsdf.marching_cubes(self.sdf.detach(), 0.0)      # (`sdf` may require grad: pointcloud_loss)
         v = (v / (res - 1) * 2.0 - 1.0) * float(self.scale.detach())
         self.verts_np, self.faces_np = v.cpu().numpy(), f.cpu().numpy().astype(np.int64)
         self.vgrad_np = np.zeros_like(self.verts_np)
@@ -377,18 +377,23 @@ class SDFGrid3D(Body3D):
         return float(self.scale.detach())
 
     def query_sdfs(self, pts_loc, return_grads=True, return_overlapmask=False):
-        return mass_properties.grid_sdf_query(self.sdf, float(self.scale.detach()), pts_loc, return_grads, return_overlapmask)
+        return mass_properties.grid_sdf_query(self.sdf.detach(), float(self.scale.detach()), pts_loc, return_grads, return_overlapmask)
 
     def pointcloud_loss(self, pts_world):
         """Body3D.pointcloud_loss with this body's own grid (dss_pointcloud_loss_grids): differentiable w.r.t. the pose, by the
-        reference's DiffGridSDF rule; the grid and the scale are constants."""
+        reference's DiffGridSDF rule, and -- where ``sdf`` was given as a tensor that requires grad -- w.r.t. the samples, by the
+        derivative of the trilinear value (dss_pointcloud_loss_grids_adjoint); the scale stays a constant."""
         from .. import grids, pointcloud
         pts = mass_properties._dev(pts_world)
-        if getattr(self, "_grid_table", None) is None:      # (the samples go to the device once)
-            self._grid_table = grids.GridTable([self.sdf], pts.device)
+        if self.sdf.requires_grad:      # (samples that are being fitted change in place between calls: their table is made per call)
+            table = grids.GridTable([self.sdf], pts.device)
+        else:
+            if getattr(self, "_grid_table", None) is None:      # (the samples go to the device once)
+                self._grid_table = grids.GridTable([self.sdf], pts.device)
+            table = self._grid_table
         prm = torch.tensor([[0.0, 0.0, 0.0, self.shape_aux()]], dtype=torch.float64, device=pts.device)
         s, n = pointcloud.match_pointcloud(pts, [0, pts.shape[0]], self.p.to(torch.float64).to(pts.device)[None],
-                                           torch.tensor([self.shape_type], dtype=torch.int32), prm, grids=self._grid_table, grid_id=[0])
+                                           torch.tensor([self.shape_type], dtype=torch.int32), prm, grids=table, grid_id=[0])
         return s[0], n[0]
 
     def _get_ang_inertia(self, mass):

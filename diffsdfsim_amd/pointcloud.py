@@ -11,7 +11,12 @@ is a multiply.  Device tensors only.
 
 Voxel-grid bodies (shape type 7): pass `grids=` (a grids.GridTable or a list of [n0,n1,n2] arrays) and `grid_id` [nseg] (-1: none);
 the call is then dss_pointcloud_loss_grids.  A grid segment's value is the trilinear field times prm[:, 3] (the scale), its pose
-Jacobian follows the reference's DiffGridSDF rule, and its prm gradient is zero.
+Jacobian follows the reference's DiffGridSDF rule, and its prm gradient is zero.  Where a grid of the table requires grad (a
+GridTable made of such tensors keeps their graph in `data`), the loss is also differentiable w.r.t. the samples: the value is
+linear in the 8 samples of a point's cell, d loss_sum / d sample_c = sum over the points of 2 phi scale w_c, and backward adds
+those terms with dss_pointcloud_loss_grids_adjoint (csrc/pointcloud_loss_grid_adj.hip; fp64 atomic adds, so two backward passes
+agree to the rounding of each sample's sum, not in bits).  The forward is the same call and returns the same bits; the scale stays a
+constant.  With no grid requiring grad nothing differs from before.
 
 Neural bodies (shape type 6, SDF3D with decode_igr): pass `igr=` (a pack_weights result or an IgrNet), `latent` [n_lat, L] and
 `latent_id` [nseg] (-1: not neural).  Those segments take prm[:, 3] as the scale and go to dss_pointcloud_loss_igr
@@ -69,6 +74,52 @@ class _MatchPointcloud(torch.autograd.Function):
         g = g_sum[:, None]
         g_prm = torch.cat([g * out[:, 9:12], out.new_zeros(out.shape[0], 1)], 1)      # the corner radius is a constant
         return None, None, None, g * out[:, 2:9], None, g_prm, None, None
+
+
+def _launch_grids_adjoint(pts, seg_off, max_len, pose, shape_type, prm, ngrid, grid_off, grid_dims, grid_data, grid_id, g_sum):
+    """dss_pointcloud_loss_grids_adjoint: -> g_data, pooled like grid_data (zeroed here, the call adds into it)."""
+    L = _lib.lib()
+    if not hasattr(L, "dss_pointcloud_loss_grids_adjoint"):      # (declared in csrc/pointcloud_loss.h, outside the public header's table)
+        raise _lib.HipLibraryError("libdiffsdfsim_hip.so does not export dss_pointcloud_loss_grids_adjoint: rebuild it (python __graft_entry__.py build)")
+    g_data = torch.zeros_like(grid_data)
+    rc = L.dss_pointcloud_loss_grids_adjoint(pose.shape[0], max_len, _lib.ptr(seg_off), _lib.ptr(pts), _lib.ptr(pose), _lib.ptr(shape_type),
+                                             _lib.ptr(prm), _lib.ptr(grid_id), ngrid, _lib.ptr(grid_off), _lib.ptr(grid_dims), _lib.ptr(grid_data),
+                                             _lib.ptr(g_sum), _lib.ptr(g_data), _lib.stream_ptr(pose.device))
+    _lib.check(rc, "dss_pointcloud_loss_grids_adjoint")
+    return g_data
+
+
+class _MatchPointcloudGridData(torch.autograd.Function):
+    """_MatchPointcloud with the table's samples as an input of the graph: `grid_data` is grids.data (a table made of grids that
+    require grad).  The forward is the same call on the same memory; the backward adds the samples' gradient."""
+
+    @staticmethod
+    def forward(ctx, pts, seg_off, max_len, pose, shape_type, prm, grids, grid_id, grid_data):
+        pose_c, prm_c = pose.detach().contiguous(), prm.detach().contiguous()
+        out = _launch(pts, seg_off, max_len, pose_c, shape_type, prm_c, grids, grid_id)
+        ctx.save_for_backward(out, pts, seg_off, pose_c, shape_type, prm_c, grids.off, grids.dims, grid_id, grid_data)
+        ctx.max_len, ctx.ngrid = max_len, grids.ngrid
+        count = out[:, 1].clone()
+        ctx.mark_non_differentiable(count)
+        return out[:, 0].clone(), count
+
+    @staticmethod
+    def backward(ctx, g_sum, _g_count):
+        out, pts, seg_off, pose, shape_type, prm, grid_off, grid_dims, grid_id, grid_data = ctx.saved_tensors
+        g = g_sum[:, None]
+        g_prm = torch.cat([g * out[:, 9:12], out.new_zeros(out.shape[0], 1)], 1)      # the corner radius is a constant
+        g_data = None
+        if ctx.needs_input_grad[8]:
+            g_data = _launch_grids_adjoint(pts, seg_off, ctx.max_len, pose, shape_type, prm, ctx.ngrid, grid_off, grid_dims, grid_data, grid_id,
+                                           g_sum.detach().to(torch.float64).contiguous())
+        return None, None, None, g * out[:, 2:9], None, g_prm, None, None, g_data
+
+
+def _match_grids(pts, seg_off, max_len, pose, shape_type, prm, table, grid_id):
+    """The loss with a grid table: through the samples' graph where the table carries one, else the call as it always was."""
+    if table is not None and table.data.requires_grad:
+        return _MatchPointcloudGridData.apply(pts, seg_off, max_len, pose, shape_type, prm, table, grid_id, table.data)
+    return _MatchPointcloud.apply(pts, seg_off, max_len, pose, shape_type, prm, table, grid_id)
 
 
 class NeuralSegmentError(_lib.HipLibraryError, ValueError):
@@ -153,7 +204,7 @@ def _match_with_neural(pts, off, pose, types, prm, grids, grid_id, igr, latent, 
                 raise ValueError("grids= needs grid_id [nseg] (-1: the segment's body has no grid)")
             T = as_table(grids, dev)
             gid = T.ids(grid_id, (nseg,), dev)[do].contiguous()
-        s, n = _MatchPointcloud.apply(p_o, off_o.to(dev, torch.int32), max_o, pose[do], types[do].contiguous(), prm[do], T, gid)
+        s, n = _match_grids(p_o, off_o.to(dev, torch.int32), max_o, pose[do], types[do].contiguous(), prm[do], T, gid)
         loss, count = loss.index_copy(0, do, s), count.index_copy(0, do, n)
     return loss, count.detach()
 
@@ -181,4 +232,4 @@ def match_pointcloud(pts, seg_off, pose, shape_type, prm, grids=None, grid_id=No
     if grid_id is None:
         raise ValueError("grids= needs grid_id [nseg] (-1: the segment's body has no grid)")
     T = as_table(grids, dev)
-    return _MatchPointcloud.apply(pts, off_d, max_len, pose, types, prm, T, T.ids(grid_id, (nseg,), dev))
+    return _match_grids(pts, off_d, max_len, pose, types, prm, T, T.ids(grid_id, (nseg,), dev))

@@ -50,6 +50,8 @@ OPTIONAL_PROTOTYPES = {
     # voxel-grid bodies in the loss and in the camera (the same two headers)
     "dss_pointcloud_loss_grids": ("i", "iippppppipppppzp"), "dss_grid_block_min": ("i", "ippppipp"),
     "dss_depth_render_grids": ("i", "iippppddddiiddpipppppppp"),
+    # the loss's adjoint w.r.t. a voxel grid's samples (csrc/pointcloud_loss.h; pointcloud.py raises where a library does not export it)
+    "dss_pointcloud_loss_grids_adjoint": ("i", "iippppppipppppp"),
     # the colour camera: shading of the depth camera's images (csrc/shade_camera.h; depth_camera.shade raises where it is not exported)
     "dss_shade_render": ("i", "iippppddddiidpippppppppipdpidppppp"),
     # recorded clouds (csrc/cloud_select.h; exported by every product library, diffsdfsim_amd/recorded.py raises where not)
