@@ -1,4 +1,4 @@
-"""Loader for the C-ABI HIP library (``include/diffsdfsim_hip.h``).
+"""Loader for the C-ABI HIP library (``include/*.h``).
 
 The product path has NO CPU fallback: if ``libdiffsdfsim_hip.so`` is missing or a tensor is
 not on a HIP device the call raises.  ``build()`` compiles the library in-tree with hipcc
@@ -95,8 +95,17 @@ def build(force=False, verbose=False, diag=False):
     return lib_path
 
 
+def bind_or_raise(L):
+    """world_abi.bind(L); a function of the headers that L does not export is a HipLibraryError that names it."""
+    try:
+        return bind(L)
+    except AttributeError as e:      # (ctypes: "<path>: undefined symbol: <name>")
+        raise HipLibraryError("the library does not export a function of include/*.h (%s): rebuild it "
+                              "(python __graft_entry__.py build)" % e) from None
+
+
 def lib():
-    """The loaded library; raises HipLibraryError if it has not been built."""
+    """The loaded library; raises HipLibraryError if it has not been built or lacks a function of the headers."""
     global _LIB
     if _LIB is None:
         if not os.path.exists(LIB_PATH):
@@ -106,7 +115,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         if L.dss_abi_version() != ABI_VERSION:      # (before bind: a library of another version may lack functions)
             raise HipLibraryError("ABI mismatch: library %d, python %d" % (L.dss_abi_version(), ABI_VERSION))
-        _LIB = bind(L)
+        _LIB = bind_or_raise(L)
     return _LIB
 
 

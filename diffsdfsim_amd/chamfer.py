@@ -1,6 +1,6 @@
 """Chamfer distance of vertex clouds on the device, for a batch of scenes in one call, with its gradient: what every experiment
 of the reference logs per iteration as `pytorch3d.loss.chamfer_distance(obj.verts, obj_target.verts)` (optim_sphere.py:244), by
-the nearest-neighbour kernel of csrc/chamfer.hip (ABI: csrc/chamfer.h).
+the nearest-neighbour kernel of csrc/chamfer.hip (ABI: include/chamfer.h).
 
     d2, idx = nearest(q, q_off, r, r_off)              # per query: squared distance to, and row of, its segment's nearest point
     c = chamfer_packed(a, a_off, b, b_off)             # [B], differentiable w.r.t. a and b
@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 
-# the launch shape of csrc/chamfer.hip (csrc/chamfer.h: DSS_CHAMFER_*), for callers and tests that pick sizes from it
+# the launch shape of csrc/chamfer.hip (include/chamfer.h: DSS_CHAMFER_*), for callers and tests that pick sizes from it
 TILE = 512             # reference points per LDS tile
 QUERIES = 512          # query points per workgroup
 SPLIT_TILES = 2        # the fewest tiles a split of the reference range is given
@@ -24,17 +24,10 @@ TARGET_WG = 2048       # workgroups the launcher aims at before it stops splitti
 
 
 def splits(nseg, max_q_len, max_r_len):
-    """The number of workgroups the launcher divides a segment's reference range among (csrc/chamfer.h); above 1 the partial
+    """The number of workgroups the launcher divides a segment's reference range among (include/chamfer.h); above 1 the partial
     minima go through the workspace and the merge kernel."""
     qblocks, tiles = -(-max_q_len // QUERIES), -(-max_r_len // TILE)
     return max(1, min(-(-tiles // SPLIT_TILES), -(-TARGET_WG // (nseg * max(qblocks, 1)))))
-
-
-def _entry(name):
-    L = _lib.lib()
-    if not hasattr(L, name):      # (declared in csrc/chamfer.h, outside the public header's table)
-        raise _lib.HipLibraryError("libdiffsdfsim_hip.so does not export %s: rebuild it (python __graft_entry__.py build)" % name)
-    return getattr(L, name)
 
 
 def _cloud(x, name, fn):
@@ -69,7 +62,7 @@ def nearest(q, q_off, r, r_off):
     if q.shape[0] == 0:
         return torch.zeros(0, dtype=torch.float64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
     max_q, max_r = int((qo[1:] - qo[:-1]).max()), int((ro[1:] - ro[:-1]).max())
-    fn, nbytes = _entry("dss_chamfer_nn"), _entry("dss_chamfer_nn_workspace_bytes")(nseg, max_q, max_r)
+    fn, nbytes = _lib.lib().dss_chamfer_nn, _lib.lib().dss_chamfer_nn_workspace_bytes(nseg, max_q, max_r)
     ws = torch.empty(max(nbytes // 8 + 1, 1), dtype=torch.float64, device=dev)
     d2 = torch.zeros(q.shape[0], dtype=torch.float64, device=dev)
     idx = torch.full((q.shape[0],), -1, dtype=torch.int32, device=dev)
@@ -85,7 +78,7 @@ def _segment_mean(v, off):
     out = torch.full((nseg,), float("nan"), dtype=torch.float64, device=v.device)
     if v.numel():
         off_d = off.to(v.device, torch.int32)
-        _lib.check(_entry("dss_chamfer_segment_mean")(nseg, _lib.ptr(off_d), _lib.ptr(v), _lib.ptr(out), _lib.stream_ptr(v.device)),
+        _lib.check(_lib.lib().dss_chamfer_segment_mean(nseg, _lib.ptr(off_d), _lib.ptr(v), _lib.ptr(out), _lib.stream_ptr(v.device)),
                    "dss_chamfer_segment_mean")
     return out
 

@@ -14,7 +14,7 @@
 //
 // All fp64 VALU work, O(Nq Nr) per segment; no atomics, so every output is a function of the input alone.
 #include "../../include/diffsdfsim_hip.h"
-#include "chamfer.h"
+#include "../../include/chamfer.h"
 #include "wave_utils.h"
 
 namespace {

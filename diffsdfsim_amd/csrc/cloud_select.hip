@@ -13,7 +13,7 @@
 // Memory-bound (4 B read per pixel and 24 B more per labelled pixel, 24 B per point); no atomics, so every output is a
 // function of the input alone.
 #include "../../include/diffsdfsim_hip.h"
-#include "cloud_select.h"
+#include "../../include/cloud_select.h"
 #include "wave_utils.h"
 
 namespace {

@@ -4,7 +4,7 @@
 // translation units compiles its own copy, and the operations are the same in both.
 #pragma once
 #include "../../include/diffsdfsim_hip.h"
-#include "depth_camera.h"
+#include "../../include/depth_camera.h"
 #include "geom.h"
 #include "wave_utils.h"
 

@@ -13,11 +13,10 @@
 // into the workspace.  A second kernel adds a segment's partials in index order.  No atomics anywhere: the summation
 // order is a function of the launch shape alone, so two calls on the same input return the same bits.
 // 24 B read per point against ~1 500 fp64 instructions (the dual-number SDF): VALU-bound, like dss_sdf_query.
-#include <vector>
-
 #include "../../include/diffsdfsim_hip.h"
+#include "pointcloud_args.h"
 #include "pointcloud_chunk.h"
-#include "pointcloud_loss.h"
+#include "../../include/pointcloud_loss.h"
 #include "pointcloud_point.h"
 #include "wave_utils.h"
 
@@ -156,19 +155,9 @@ int dss_pointcloud_loss(int nseg, int max_seg_len, const int *seg_off, const dou
     if ((long long)nseg * pc_chunks(max_seg_len) > 0x7fffffffLL / PC_OUT) return DSS_E_UNSUPPORTED;      // grid.x, int indices
     const size_t need = dss_pointcloud_loss_workspace_bytes(nseg, max_seg_len);
     if (need > 0 && (!workspace || workspace_bytes < need)) return DSS_E_WORKSPACE;
-    // the shape types decide the status, so the host reads them (nseg ints) before anything is enqueued
+    // the shape types decide the status (neural and grid bodies: not in this loss), so the host reads them before anything is enqueued
     hipStream_t st = (hipStream_t)stream;
-#if defined(DSS_EMU)
-    const int *types = shape_type;      // (the emulator's device memory is the host's)
-#else
-    std::vector<int> host_types(nseg);
-    if (hipMemcpyAsync(host_types.data(), shape_type, sizeof(int) * (size_t)nseg, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return DSS_E_BADARG;
-    const int *types = host_types.data();
-#endif
-    for (int s = 0; s < nseg; ++s)
-        if (types[s] < DSS_SHAPE_BOX || types[s] > DSS_SHAPE_BOWL) return DSS_E_UNSUPPORTED;      // neural and grid bodies: not in this loss
+    if (const int rc = pc_judge_segments(nseg, shape_type, nullptr, 0, nullptr, st)) return rc;
     const int chunks = pc_chunks(max_seg_len);
     if (chunks > 0)
         hipLaunchKernelGGL(pointcloud_loss_kernel, dim3(chunks * nseg), dim3(PC_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,
@@ -190,27 +179,7 @@ int dss_pointcloud_loss_grids(int nseg, int max_seg_len, const int *seg_off, con
     if (need > 0 && (!workspace || workspace_bytes < need)) return DSS_E_WORKSPACE;
     // shape types, grid ids and the grids' dims decide the status: the host reads them before anything is enqueued
     hipStream_t st = (hipStream_t)stream;
-#if defined(DSS_EMU)
-    const int *types = shape_type, *ids = grid_id, *dims = grid_dims;      // (the emulator's device memory is the host's)
-#else
-    std::vector<int> host_types(nseg), host_ids(nseg), host_dims(3 * (size_t)ngrid);
-    if (hipMemcpyAsync(host_types.data(), shape_type, sizeof(int) * (size_t)nseg, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(host_ids.data(), grid_id, sizeof(int) * (size_t)nseg, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (ngrid > 0 && hipMemcpyAsync(host_dims.data(), grid_dims, sizeof(int) * 3 * (size_t)ngrid, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return DSS_E_BADARG;
-    const int *types = host_types.data(), *ids = host_ids.data(), *dims = host_dims.data();
-#endif
-    for (int g = 0; g < 3 * ngrid; ++g)
-        if (dims[g] < 2) return DSS_E_BADARG;
-    for (int s = 0; s < nseg; ++s) {
-        if (types[s] == DSS_SHAPE_GRID) {
-            if (ids[s] >= ngrid) return DSS_E_BADARG;
-            if (ids[s] < 0) return DSS_E_UNSUPPORTED;      // a grid body without a grid
-        } else if (types[s] < DSS_SHAPE_BOX || types[s] > DSS_SHAPE_BOWL) {
-            return DSS_E_UNSUPPORTED;      // neural bodies: the network is not in this loss
-        }
-    }
+    if (const int rc = pc_judge_segments(nseg, shape_type, grid_id, ngrid, grid_dims, st)) return rc;
     const int chunks = pc_chunks(max_seg_len);
     if (chunks > 0)
         hipLaunchKernelGGL(pointcloud_loss_grids_kernel, dim3(chunks * nseg), dim3(PC_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,

@@ -12,11 +12,10 @@
 // (-munsafe-fp-atomics: no compare-and-swap loop), as g_verts in step_bwd_all.hip and the 2-D grid adjoint do.  The order of the
 // adds into one sample is the order of arrival: two calls agree to the rounding of an n-term sum, not in their bits.  Nothing is
 // merged before the adds.
-#include <vector>
-
 #include "../../include/diffsdfsim_hip.h"
+#include "pointcloud_args.h"
 #include "pointcloud_chunk.h"
-#include "pointcloud_loss.h"
+#include "../../include/pointcloud_loss.h"
 #include "pointcloud_point.h"
 
 namespace {
@@ -71,29 +70,8 @@ extern "C" int dss_pointcloud_loss_grids_adjoint(int nseg, int max_seg_len, cons
     if ((long long)nseg * pc_chunks(max_seg_len) > 0x7fffffffLL / PC_OUT) return DSS_E_UNSUPPORTED;      // the forward's limit (grid.x, its partials)
     // shape types, grid ids and the grids' dims decide the status, as in dss_pointcloud_loss_grids: the host reads them first
     hipStream_t st = (hipStream_t)stream;
-#if defined(DSS_EMU)
-    const int *types = shape_type, *ids = grid_id, *dims = grid_dims;      // (the emulator's device memory is the host's)
-#else
-    std::vector<int> host_types(nseg), host_ids(nseg), host_dims(3 * (size_t)ngrid);
-    if (hipMemcpyAsync(host_types.data(), shape_type, sizeof(int) * (size_t)nseg, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(host_ids.data(), grid_id, sizeof(int) * (size_t)nseg, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (ngrid > 0 && hipMemcpyAsync(host_dims.data(), grid_dims, sizeof(int) * 3 * (size_t)ngrid, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return DSS_E_BADARG;
-    const int *types = host_types.data(), *ids = host_ids.data(), *dims = host_dims.data();
-#endif
-    for (int g = 0; g < 3 * ngrid; ++g)
-        if (dims[g] < 2) return DSS_E_BADARG;
     bool any = false;
-    for (int s = 0; s < nseg; ++s) {
-        if (types[s] == DSS_SHAPE_GRID) {
-            if (ids[s] >= ngrid) return DSS_E_BADARG;
-            if (ids[s] < 0) return DSS_E_UNSUPPORTED;      // a grid body without a grid
-            any = true;
-        } else if (types[s] < DSS_SHAPE_BOX || types[s] > DSS_SHAPE_BOWL) {
-            return DSS_E_UNSUPPORTED;      // neural bodies: the network is not in this loss
-        }
-    }
+    if (const int rc = pc_judge_segments(nseg, shape_type, grid_id, ngrid, grid_dims, st, &any)) return rc;
     const int chunks = pc_chunks(max_seg_len);
     if (!any || chunks == 0) return DSS_OK;      // no grid segment, or no point: nothing to add
     hipLaunchKernelGGL(pointcloud_grid_adjoint_kernel, dim3(chunks * nseg), dim3(PC_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,

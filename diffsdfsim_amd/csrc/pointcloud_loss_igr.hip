@@ -29,7 +29,7 @@
 #include "../../include/diffsdfsim_hip.h"
 #include "geom.h"
 #include "launchers.h"
-#include "pointcloud_loss_igr.h"
+#include "../../include/pointcloud_loss_igr.h"
 #include "wave_utils.h"
 
 namespace {

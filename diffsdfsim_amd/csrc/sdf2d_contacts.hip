@@ -20,7 +20,7 @@
 
 #include "../../include/diffsdfsim_hip.h"
 #include "geom.h"
-#include "sdf2d_contacts.h"
+#include "../../include/sdf2d_contacts.h"
 #include "wrap2d.h"
 
 namespace {

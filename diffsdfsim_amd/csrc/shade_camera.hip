@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "depth_trace.h"
-#include "shade_camera.h"
+#include "../../include/shade_camera.h"
 
 namespace {
 

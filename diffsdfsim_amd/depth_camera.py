@@ -1,6 +1,6 @@
 """Depth camera on the device: what the experiment's Recorder3D(record_points=True, record_seg=True) records and what
 match_pointcloud (experiments/trajectory_fitting/optim_pointcloud.py:168-187) selects from it, by the kernels of
-csrc/depth_camera.hip (ABI: csrc/depth_camera.h).
+csrc/depth_camera.hip (ABI: include/depth_camera.h).
 
     depth, seg = render_depth(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640, 480))
     pts, seg_off = observed_points(depth, seg, body, cam_pose, fx, fy, cx, cy)
@@ -17,7 +17,7 @@ Voxel-grid bodies: `grids=` a grids.GridTable (or a list of [n0,n1,n2] arrays) a
 shape type 7 (SDFGrid3D) and 6 (a neural SDF3D, seen through the value grid its mesh is extracted from: body_grid) into the
 same images, by dss_depth_render_grids; brick, bowl and a grid or neural body without a grid still raise.
 
-The colour camera (csrc/shade_camera.hip, ABI: csrc/shade_camera.h) shades those images: surface normals, Lambert shading by up to
+The colour camera (csrc/shade_camera.hip, ABI: include/shade_camera.h) shades those images: surface normals, Lambert shading by up to
 four directional lights with hard shadows, the bodies' colours; physics3d.utils.Recorder3D records through it.
 
     rgb, normal, shade, flags = shade(depth, seg, pose, shape_type, prm, cam_pose, fx, fy, cx, cy, colors, lights)
@@ -31,13 +31,6 @@ import torch
 from . import _lib
 
 MAX_BODIES = 8
-
-
-def _entry(name):
-    L = _lib.lib()
-    if not hasattr(L, name):      # (declared in csrc/depth_camera.h, outside the public header's table)
-        raise _lib.HipLibraryError("libdiffsdfsim_hip.so does not export %s: rebuild it (python __graft_entry__.py build)" % name)
-    return getattr(L, name)
 
 
 def _camera(cam_pose, dev):
@@ -80,17 +73,17 @@ def render_depth(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640, 480
         if grid_id is None:
             raise ValueError("grids= needs grid_id [nview,nbody] (-1: the body has no grid)")
         ids = T.ids(grid_id, (nview, nbody), dev)
-        rc = _entry("dss_depth_render_grids")(nview, nbody, _lib.ptr(pose), _lib.ptr(types), _lib.ptr(prm), _lib.ptr(cam), fx, fy, cx, cy, W, H,
-                                              float(znear), float(zfar), _lib.ptr(ids), T.ngrid, _lib.ptr(T.off), _lib.ptr(T.dims),
-                                              _lib.ptr(T.data), _lib.ptr(T.blk_off), _lib.ptr(T.block_min()), _lib.ptr(depth), _lib.ptr(seg),
-                                              _lib.stream_ptr(dev))
+        rc = _lib.lib().dss_depth_render_grids(nview, nbody, _lib.ptr(pose), _lib.ptr(types), _lib.ptr(prm), _lib.ptr(cam), fx, fy, cx, cy, W, H,
+                                               float(znear), float(zfar), _lib.ptr(ids), T.ngrid, _lib.ptr(T.off), _lib.ptr(T.dims),
+                                               _lib.ptr(T.data), _lib.ptr(T.blk_off), _lib.ptr(T.block_min()), _lib.ptr(depth), _lib.ptr(seg),
+                                               _lib.stream_ptr(dev))
         if rc == -3:
             raise _lib.HipLibraryError("dss_depth_render_grids: the renderer takes shape types 0-3 and, with a grid_id >= 0, grid and "
                                        "neural bodies (7, 6); got types %s with grid ids %s" %
                                        (sorted(set(types.reshape(-1).tolist())), sorted(set(ids.reshape(-1).tolist()))))
         _lib.check(rc, "dss_depth_render_grids")
         return depth, seg
-    fn = _entry("dss_depth_render")
+    fn = _lib.lib().dss_depth_render
     rc = fn(nview, nbody, _lib.ptr(pose), _lib.ptr(types), _lib.ptr(prm), _lib.ptr(cam),
             fx, fy, cx, cy, W, H, float(znear), float(zfar), _lib.ptr(depth), _lib.ptr(seg), _lib.stream_ptr(dev))
     if rc == -3:
@@ -114,7 +107,7 @@ def observed_points(depth, seg, body, cam_pose, fx, fy, cx, cy):
     fx, fy, cx, cy = _intrinsics(fx, fy, cx, cy)
     dev = depth.device
     depth, seg = depth.contiguous(), seg.contiguous()
-    count, emit = _entry("dss_depth_points_count"), _entry("dss_depth_points_emit")
+    count, emit = _lib.lib().dss_depth_points_count, _lib.lib().dss_depth_points_emit
     rows = torch.zeros(nview * H, dtype=torch.int32, device=dev)
     _lib.check(count(nview, H, W, int(body), _lib.ptr(depth), _lib.ptr(seg), _lib.ptr(rows), _lib.stream_ptr(dev)), "dss_depth_points_count")
     incl = torch.cumsum(rows, 0, dtype=torch.int64)
@@ -174,7 +167,7 @@ def _lights(lights, dev):
 
 def shade(depth, seg, pose, shape_type, prm, cam_pose, fx, fy, cx, cy, colors, lights, ambient=0.1, background=(1, 1, 1), shadows=True,
           shadow_bias=1e-3, zfar=100.0, grids=None, grid_id=None):
-    """Shade the images render_depth returned for the same views (dss_shade_render, csrc/shade_camera.h): the surface normal at
+    """Shade the images render_depth returned for the same views (dss_shade_render, include/shade_camera.h): the surface normal at
     every hit, Lambert shading by the lights with hard shadows, the bodies' colours.
     colors [nview,nbody,3] (or [nbody,3] for every view) in [0, 1]; lights: up to four (direction TOWARDS the light, intensity)
     in the world frame; ambient the shade of a surface no light reaches; background the colour of a pixel that hit nothing.
@@ -197,7 +190,7 @@ def shade(depth, seg, pose, shape_type, prm, cam_pose, fx, fy, cx, cy, colors, l
         raise ValueError("shadow_bias > 0 and zfar > 0, got %r, %r" % (shadow_bias, zfar))
     fx, fy, cx, cy = _intrinsics(fx, fy, cx, cy)
     dev = depth.device
-    fn = _entry("dss_shade_render")
+    fn = _lib.lib().dss_shade_render
     types = torch.as_tensor(shape_type).to(dev, torch.int32).reshape(nview, nbody).contiguous()
     col = torch.as_tensor(colors, dtype=torch.float64).to(dev)
     col = (col.expand(nview, nbody, 3) if col.dim() == 2 else col.reshape(nview, nbody, 3)).contiguous()

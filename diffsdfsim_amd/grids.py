@@ -1,4 +1,4 @@
-"""Pooled voxel grids on the device, for the depth camera and the point-cloud loss (csrc/depth_camera.h, csrc/pointcloud_loss.h).
+"""Pooled voxel grids on the device, for the depth camera and the point-cloud loss (include/depth_camera.h, include/pointcloud_loss.h).
 
     table = GridTable([sdf_a, sdf_b, ...])      # each [n0,n1,n2] float64, x slowest, n_d >= 2
     render_depth(..., grids=table, grid_id=...) / match_pointcloud(..., grids=table, grid_id=...)
@@ -64,8 +64,6 @@ class GridTable:
         """[nblk] float64: per block the least of its corner samples, grid after grid, x slowest (dss_grid_block_min)."""
         if self._blk_min is None:
             L = _lib.lib()
-            if not hasattr(L, "dss_grid_block_min"):
-                raise _lib.HipLibraryError("libdiffsdfsim_hip.so does not export dss_grid_block_min: rebuild it (python __graft_entry__.py build)")
             out = torch.empty(self.nblk, dtype=torch.float64, device=self.device)
             _lib.check(L.dss_grid_block_min(self.ngrid, _lib.ptr(self.off), _lib.ptr(self.dims), _lib.ptr(self.data.detach()), _lib.ptr(self.blk_off),
                                             self.nblk, _lib.ptr(out), _lib.stream_ptr(self.device)), "dss_grid_block_min")

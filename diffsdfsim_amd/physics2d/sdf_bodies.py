@@ -46,7 +46,7 @@ def _ring(n):
 
 class SDF(Body):
     kind = 2              # an SDF body to the world's pair dispatch (0: circle, 1: convex polygon)
-    sdf_kind = -1         # DSS_SDF2D_<kind> of csrc/sdf2d_contacts.h
+    sdf_kind = -1         # DSS_SDF2D_<kind> of include/sdf2d_contacts.h
 
     def __init__(self, pos, scale, vel=(0, 0, 0), mass=1, restitution=Defaults.RESTITUTION, fric_coeff=Defaults.FRIC_COEFF,
                  eps=Defaults.EPSILON, col=(255, 0, 0), thickness=1):

@@ -2,7 +2,7 @@
 
 `sdf_physics.physics.contacts.SDFContactHandler` walks every edge of one body's outline with a Frank-Wolfe search over the
 other body's SDF, in both directions, and thins what it finds by a PCA and a convex hull.  `csrc/sdf2d_contacts.hip`
-(``dss_sdf2d_contacts_forward`` / ``_backward``, csrc/sdf2d_contacts.h) does that for P pairs per launch, one wavefront per
+(``dss_sdf2d_contacts_forward`` / ``_backward``, include/sdf2d_contacts.h) does that for P pairs per launch, one wavefront per
 pair; `sdf_contacts2d` is the batched, differentiable operator, `SDFContactHandler` the class for the reference's
 ``World(..., contact_callback=SDFContactHandler)``, and `physics2d.World` sends its pairs of SDF bodies here.
 
@@ -59,11 +59,6 @@ class GridTable:
 
 
 def _kernels(get_lib, on_device):
-    def entry(L, name):
-        if not hasattr(L, name):
-            raise _lib.HipLibraryError("the library does not export %s (csrc/sdf2d_contacts.hip): rebuild it" % name)
-        return getattr(L, name)
-
     def ptr(t):
         return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)
 
@@ -81,7 +76,7 @@ def _kernels(get_lib, on_device):
         if cand_cap:
             ncand = torch.empty(P, dtype=torch.int32, device=dev)
             cand, cand_tag = torch.empty(P, cand_cap, 7, dtype=torch.float64, device=dev), torch.empty(P, cand_cap, 2, dtype=torch.int32, device=dev)
-        rc = entry(get_lib(), "dss_sdf2d_contacts_forward")(
+        rc = get_lib().dss_sdf2d_contacts_forward(
             P, cap, ptr(kind), ptr(pose), ptr(prm), ptr(scale), ptr(grid_id), grids.address() if grids is not None else None, eps,
             ptr(out), ptr(count), ptr(status), ptr(tag), ptr(tpar), cand_cap, ptr(ncand), ptr(cand), ptr(cand_tag), stream(pose))
         _lib.check(rc, "dss_sdf2d_contacts_forward")
@@ -90,7 +85,7 @@ def _kernels(get_lib, on_device):
     def backward(kind, pose, prm, scale, grid_id, grids, cap, count, tag, tpar, gout):
         P = pose.shape[1]
         g_pose, g_prm, g_scale = torch.zeros_like(pose), torch.zeros_like(prm), torch.zeros_like(scale)
-        rc = entry(get_lib(), "dss_sdf2d_contacts_backward")(
+        rc = get_lib().dss_sdf2d_contacts_backward(
             P, cap, ptr(kind), ptr(pose), ptr(prm), ptr(scale), ptr(grid_id), grids.address() if grids is not None else None,
             ptr(count), ptr(tag), ptr(tpar), ptr(gout), ptr(g_pose), ptr(g_prm), ptr(g_scale), stream(pose))
         _lib.check(rc, "dss_sdf2d_contacts_backward")
@@ -102,7 +97,7 @@ def _kernels(get_lib, on_device):
         g_pose, g_prm, g_scale = torch.zeros_like(pose), torch.zeros_like(prm), torch.zeros_like(scale)
         # (one element at least: a table whose grids have no outline is no null argument)
         g_tab = [torch.zeros(max(grids.tensors[k].numel(), 1), dtype=torch.float64, device=pose.device) for k in ("vals", "grads", "verts")]
-        rc = entry(get_lib(), "dss_sdf2d_contacts_backward_grids")(
+        rc = get_lib().dss_sdf2d_contacts_backward_grids(
             P, cap, ptr(kind), ptr(pose), ptr(prm), ptr(scale), ptr(grid_id), grids.address(), ptr(count), ptr(tag), ptr(tpar), ptr(gout),
             ptr(g_pose), ptr(g_prm), ptr(g_scale), ptr(g_tab[0]), ptr(g_tab[1]), ptr(g_tab[2]), stream(pose))
         _lib.check(rc, "dss_sdf2d_contacts_backward_grids")
@@ -115,7 +110,9 @@ DEVICE_KERNELS = _kernels(_lib.lib, True)
 
 
 def host_kernels(L):
-    """The same entry points of a library that runs on host memory (the CPU emulator build of the tests)."""
+    """The same entry points of a library that runs on host memory (the CPU emulator build of the tests), held to the
+    headers like the product's."""
+    _lib.bind_or_raise(L)
     return _kernels(lambda: L, False)
 
 

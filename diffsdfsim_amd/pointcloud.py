@@ -35,7 +35,7 @@ from . import _lib
 from .world_abi import SHAPE_IGR
 
 OUT = 12      # sum, count, d / d pose [7], d / d prm [3]
-OUT_IGR = 13  # sum, count, d / d pose [7], d / d latent [4]
+OUT_IGR = 13  # DSS_PC_IGR_OUT: sum, count, d / d pose [7], d / d latent [4]
 
 
 def _launch(pts, seg_off, max_len, pose, shape_type, prm, grids=None, grid_id=None):
@@ -43,8 +43,6 @@ def _launch(pts, seg_off, max_len, pose, shape_type, prm, grids=None, grid_id=No
     nseg = pose.shape[0]
     L = _lib.lib()
     name = "dss_pointcloud_loss" if grids is None else "dss_pointcloud_loss_grids"
-    if not hasattr(L, name):      # (declared in csrc/pointcloud_loss.h, outside the public header's table)
-        raise _lib.HipLibraryError("libdiffsdfsim_hip.so does not export %s: rebuild it (python __graft_entry__.py build)" % name)
     out = torch.zeros(nseg, OUT, dtype=torch.float64, device=pose.device)
     nbytes = L.dss_pointcloud_loss_workspace_bytes(nseg, max_len)
     ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=pose.device)
@@ -79,8 +77,6 @@ class _MatchPointcloud(torch.autograd.Function):
 def _launch_grids_adjoint(pts, seg_off, max_len, pose, shape_type, prm, ngrid, grid_off, grid_dims, grid_data, grid_id, g_sum):
     """dss_pointcloud_loss_grids_adjoint: -> g_data, pooled like grid_data (zeroed here, the call adds into it)."""
     L = _lib.lib()
-    if not hasattr(L, "dss_pointcloud_loss_grids_adjoint"):      # (declared in csrc/pointcloud_loss.h, outside the public header's table)
-        raise _lib.HipLibraryError("libdiffsdfsim_hip.so does not export dss_pointcloud_loss_grids_adjoint: rebuild it (python __graft_entry__.py build)")
     g_data = torch.zeros_like(grid_data)
     rc = L.dss_pointcloud_loss_grids_adjoint(pose.shape[0], max_len, _lib.ptr(seg_off), _lib.ptr(pts), _lib.ptr(pose), _lib.ptr(shape_type),
                                              _lib.ptr(prm), _lib.ptr(grid_id), ngrid, _lib.ptr(grid_off), _lib.ptr(grid_dims), _lib.ptr(grid_data),
@@ -132,8 +128,6 @@ def _launch_igr(pts, seg_off, max_len, pose, scale, packed, latent, lat_idx):
     from .igr import net_struct
     nseg, n_pts = pose.shape[0], pts.shape[0]
     L = _lib.lib()
-    if not hasattr(L, "dss_pointcloud_loss_igr"):      # (declared in csrc/pointcloud_loss_igr.h, outside the public header's table)
-        raise _lib.HipLibraryError("libdiffsdfsim_hip.so does not export dss_pointcloud_loss_igr: rebuild it (python __graft_entry__.py build)")
     out = torch.zeros(nseg, OUT_IGR, dtype=torch.float64, device=pose.device)
     nbytes = L.dss_pointcloud_loss_igr_workspace_bytes(nseg, max_len, n_pts)
     ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=pose.device)

@@ -1,6 +1,6 @@
 """Recorded RGB-D sequences on the device: the observations of experiments/trajectory_fitting/optim_pointcloud_real.py in the
 form that script reads them, the selection of the thrown body's points from them and the statistics it initialises from, by
-the kernels of csrc/cloud_select.hip (ABI: csrc/cloud_select.h).
+the kernels of csrc/cloud_select.hip (ABI: include/cloud_select.h).
 
     rec = load_recording(path)                         # dict(pcs [T,H,W,3], segs [T,H,W], planes [P,4], grav_dir [3], g, ...)
     pts, seg_off = select_points(rec["pcs"], rec["segs"], label=4)
@@ -21,13 +21,6 @@ from . import _lib
 
 LABEL = 4      # the thrown body's label in the recorded segmentations (optim_pointcloud_real.py:153)
 STATS = 10     # count, sum [3], min [3], max [3]
-
-
-def _entry(name):
-    L = _lib.lib()
-    if not hasattr(L, name):      # (declared in csrc/cloud_select.h, outside the public header's table)
-        raise _lib.HipLibraryError("libdiffsdfsim_hip.so does not export %s: rebuild it (python __graft_entry__.py build)" % name)
-    return getattr(L, name)
 
 
 def load_recording(path, device=None):
@@ -80,7 +73,7 @@ def select_points(pcs, segs, label=LABEL):
         raise ValueError("at least one pixel and T * H * W < 2^31, got %s" % (tuple(segs.shape),))
     dev = pcs.device
     pcs, segs = pcs.detach().contiguous(), segs.contiguous()
-    count, emit = _entry("dss_cloud_select_count"), _entry("dss_cloud_select_emit")
+    count, emit = _lib.lib().dss_cloud_select_count, _lib.lib().dss_cloud_select_emit
     rows = torch.zeros(T * H, dtype=torch.int32, device=dev)
     _lib.check(count(T, H, W, int(label), _lib.ptr(pcs), _lib.ptr(segs), _lib.ptr(rows), _lib.stream_ptr(dev)), "dss_cloud_select_count")
     incl = torch.cumsum(rows, 0, dtype=torch.int64)
@@ -106,7 +99,7 @@ def _stats(pts, seg_off):
         raise ValueError("seg_off: nseg + 1 >= 2 ascending offsets into pts (below 2^31)")
     dev = pts.device
     max_len = int((off[1:] - off[:-1]).max())
-    fn, nbytes = _entry("dss_cloud_stats"), _entry("dss_cloud_stats_workspace_bytes")(nseg, max_len)
+    fn, nbytes = _lib.lib().dss_cloud_stats, _lib.lib().dss_cloud_stats_workspace_bytes(nseg, max_len)
     ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
     out = torch.zeros(nseg, STATS, dtype=torch.float64, device=dev)
     off_d, pts = off.to(dev, torch.int32), pts.detach().contiguous()

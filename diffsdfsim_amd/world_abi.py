@@ -1,9 +1,9 @@
-"""The C ABI of include/diffsdfsim_hip.h as ctypes sees it: constants, function prototypes, struct mirrors, array shapes.
+"""The C ABI of include/*.h as ctypes sees it: constants, function prototypes, struct mirrors, array shapes.
 
-The header is the documentation and the check, the tables below are the binding: ``bind()`` gives every function of a
+The headers are the documentation and the check, the tables below are the binding: ``bind()`` gives every function of a
 loaded library its ``argtypes`` / ``restype``, so callers pass plain Python ints, floats and pointers.  The field order of
 ``FIELDS`` IS the struct layout; ``dss_world_sizeof()`` is checked against it when the world is first bound to the library.
-tests/test_abi.py checks constants, prototypes and field names and their order against the header's text.
+tests/test_abi.py checks constants, prototypes and field names and their order against the headers' text.
 """
 import ctypes
 
@@ -21,8 +21,9 @@ IGR_LATENT_MAX = 4
 _I, _D, _P = ctypes.c_int, ctypes.c_double, ctypes.c_void_p
 
 # name: (return kind, argument kinds): 'p' any pointer (tensor, struct by reference, stream; None = NULL), 'i' int, 'd' double,
-# 'z' size_t, 'v' void.  In the header's order, one section per line or two.
+# 'z' size_t, 'v' void.  In the headers' order, one section per line or two.
 PROTOTYPES = {
+    # diffsdfsim_hip.h
     "dss_abi_version": ("i", ""),
     "dss_lcp_dense_workspace_bytes": ("z", "iiii"), "dss_lcp_dense_forward": ("i", "pppppppiiiidiiipppppppzp"),
     "dss_lcp_dense_backward": ("i", "ppppiiiipppppppppppppzp"),
@@ -38,32 +39,29 @@ PROTOTYPES = {
     "dss_mc_workspace_bytes": ("z", "iii"), "dss_mc_count": ("i", "piiidppzpp"), "dss_mc_emit": ("i", "piiidppipppp"),
     "dss_meshsdf_backward": ("i", "ipppipp"),
     "dss_contacts2d_forward": ("i", "iippppppdpppp"), "dss_contacts2d_backward": ("i", "iippppppdppppp"),
-}
-# outside the public header, bound where a library exports them: the diagnostic build (csrc/diag_stamps.h,
-# csrc/diag_latency.hip), the CPU emulator's test hook (tests/emu/lcp_dense_wave.cpp) and the point-cloud loss
-# (csrc/pointcloud_loss.h; every product library exports it, diffsdfsim_amd/pointcloud.py raises where one does not)
-OPTIONAL_PROTOTYPES = {
+    # pointcloud_loss.h
     "dss_pointcloud_loss_workspace_bytes": ("z", "ii"), "dss_pointcloud_loss": ("i", "iipppppppzp"),
-    # the depth camera (csrc/depth_camera.h; exported by every product library, diffsdfsim_amd/depth_camera.py raises where not)
-    "dss_depth_render": ("i", "iippppddddiiddppp"), "dss_depth_points_count": ("i", "iiiipppp"),
+    "dss_pointcloud_loss_grids": ("i", "iippppppipppppzp"), "dss_pointcloud_loss_grids_adjoint": ("i", "iippppppipppppp"),
+    # pointcloud_loss_igr.h
+    "dss_pointcloud_loss_igr_workspace_bytes": ("z", "iii"), "dss_pointcloud_loss_igr": ("i", "piippppppiippzp"),
+    # depth_camera.h
+    "dss_depth_render": ("i", "iippppddddiiddppp"), "dss_grid_block_min": ("i", "ippppipp"),
+    "dss_depth_render_grids": ("i", "iippppddddiiddpipppppppp"), "dss_depth_points_count": ("i", "iiiipppp"),
     "dss_depth_points_emit": ("i", "iiiippppddddpp"),
-    # voxel-grid bodies in the loss and in the camera (the same two headers)
-    "dss_pointcloud_loss_grids": ("i", "iippppppipppppzp"), "dss_grid_block_min": ("i", "ippppipp"),
-    "dss_depth_render_grids": ("i", "iippppddddiiddpipppppppp"),
-    # the loss's adjoint w.r.t. a voxel grid's samples (csrc/pointcloud_loss.h; pointcloud.py raises where a library does not export it)
-    "dss_pointcloud_loss_grids_adjoint": ("i", "iippppppipppppp"),
-    # the colour camera: shading of the depth camera's images (csrc/shade_camera.h; depth_camera.shade raises where it is not exported)
+    # shade_camera.h
     "dss_shade_render": ("i", "iippppddddiidpippppppppipdpidppppp"),
-    # recorded clouds (csrc/cloud_select.h; exported by every product library, diffsdfsim_amd/recorded.py raises where not)
+    # cloud_select.h
     "dss_cloud_select_count": ("i", "iiiipppp"), "dss_cloud_select_emit": ("i", "iiiippppp"),
     "dss_cloud_stats_workspace_bytes": ("z", "ii"), "dss_cloud_stats": ("i", "iippppzp"),
-    # chamfer distance (csrc/chamfer.h; exported by every product library, diffsdfsim_amd/chamfer.py raises where not)
+    # chamfer.h
     "dss_chamfer_nn_workspace_bytes": ("z", "iii"), "dss_chamfer_nn": ("i", "iiipppppppzp"), "dss_chamfer_segment_mean": ("i", "ipppp"),
-    # the point-cloud loss of neural bodies (csrc/pointcloud_loss_igr.h; pointcloud._launch_igr raises where a library does not export it)
-    "dss_pointcloud_loss_igr_workspace_bytes": ("z", "iii"), "dss_pointcloud_loss_igr": ("i", "piippppppiippzp"),
-    # contacts of 2-D SDF bodies (csrc/sdf2d_contacts.h; physics2d/sdf_contacts.py raises where a library does not export it)
+    # sdf2d_contacts.h
     "dss_sdf2d_contacts_forward": ("i", "iippppppdpppppipppp"), "dss_sdf2d_contacts_backward": ("i", "iipppppppppppppp"),
     "dss_sdf2d_contacts_backward_grids": ("i", "iippppppppppppppppp"),
+}
+# outside the headers, bound where a library exports them: the diagnostic build (csrc/diag_stamps.h, csrc/diag_latency.hip)
+# and the CPU emulator's test hooks (tests/emu/lcp_dense_wave.cpp)
+OPTIONAL_PROTOTYPES = {
     "dss_diag_set_lcp_stamps": ("v", "pp"), "dss_diag_set_np_stamps": ("v", "pp"), "dss_diag_latency": ("v", "iiippppp"),
     "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"], "dss_emu_lcp_dense_group_fits": ("i", "iii"),
 }
@@ -87,7 +85,7 @@ class DssIgrNet(ctypes.Structure):
     _fields_ = [(k, _P if k in IGR_NET_POINTERS else _I) for k in IGR_NET_FIELDS]
 
 
-SDF2D_CIRCLE, SDF2D_RECT, SDF2D_BOWL, SDF2D_GRID = 0, 1, 2, 3      # DSS_SDF2D_<kind> (csrc/sdf2d_contacts.h)
+SDF2D_CIRCLE, SDF2D_RECT, SDF2D_BOWL, SDF2D_GRID = 0, 1, 2, 3      # DSS_SDF2D_<kind> (sdf2d_contacts.h)
 SDF2D_MAXCAND = 256
 SDF2D_OVER_CAP, SDF2D_OVER_CAND, SDF2D_MALFORMED = 1, 2, 4
 SDF2D_GRID_FIELDS = ("dims", "val_off", "vert_off", "edge_off", "edges", "vals", "grads", "verts")

@@ -1,8 +1,8 @@
 // chamfer.h -- C ABI of the segmented nearest-neighbour search behind the chamfer distance of level-set meshes
-// (csrc/chamfer.hip), exported by libdiffsdfsim_hip.so beside the functions of include/diffsdfsim_hip.h, whose conventions it
+// (csrc/chamfer.hip), exported by libdiffsdfsim_hip.so beside the functions of diffsdfsim_hip.h, whose conventions it
 // shares (device pointers into caller-owned memory, double = binary64 row-major, int = int32, stream = hipStream_t as void*,
-// DSS_E_* return codes).  Bound by world_abi.OPTIONAL_PROTOTYPES; diffsdfsim_amd/chamfer.py raises if the library does not
-// export it.
+// DSS_E_* return codes).  Part of the checked ABI: bound by world_abi.PROTOTYPES, which tests/test_abi.py holds to these
+// declarations.
 #pragma once
 #include <stddef.h>
 

@@ -1,8 +1,8 @@
 // cloud_select.h -- C ABI of the selection of a labelled body's points from recorded organised clouds and of the per-segment
 // statistics of the selected points (csrc/cloud_select.hip), exported by libdiffsdfsim_hip.so beside the functions of
-// include/diffsdfsim_hip.h, whose conventions it shares (device pointers into caller-owned memory, double = binary64
-// row-major, int = int32, stream = hipStream_t as void*, DSS_E_* return codes).  Bound by world_abi.OPTIONAL_PROTOTYPES;
-// diffsdfsim_amd/recorded.py raises if the library does not export it.
+// diffsdfsim_hip.h, whose conventions it shares (device pointers into caller-owned memory, double = binary64
+// row-major, int = int32, stream = hipStream_t as void*, DSS_E_* return codes).  Part of the checked ABI: bound by
+// world_abi.PROTOTYPES, which tests/test_abi.py holds to these declarations.
 #pragma once
 #include <stddef.h>
 

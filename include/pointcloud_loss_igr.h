@@ -1,11 +1,11 @@
 // pointcloud_loss_igr.h -- C ABI of the point-cloud loss of neural (decode_igr) bodies (csrc/pointcloud_loss_igr.hip), exported by
-// libdiffsdfsim_hip.so beside the functions of include/diffsdfsim_hip.h, whose conventions it shares (device pointers into
-// caller-owned memory, double = binary64 row-major, int = int32, stream = hipStream_t as void*, DSS_E_* return codes).  Bound by
-// world_abi.OPTIONAL_PROTOTYPES; diffsdfsim_amd/pointcloud.py raises if the library does not export it.
+// libdiffsdfsim_hip.so beside the functions of diffsdfsim_hip.h, whose conventions it shares (device pointers into
+// caller-owned memory, double = binary64 row-major, int = int32, stream = hipStream_t as void*, DSS_E_* return codes).  Part of
+// the checked ABI: bound by world_abi.PROTOTYPES, which tests/test_abi.py holds to these declarations.
 #pragma once
 #include <stddef.h>
 
-#include "../../include/diffsdfsim_hip.h"
+#include "diffsdfsim_hip.h"
 
 #ifdef __cplusplus
 extern "C" {

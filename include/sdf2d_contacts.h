@@ -1,8 +1,8 @@
 // sdf2d_contacts.h -- C ABI of the 2-D SDF contact search (csrc/sdf2d_contacts.hip): the reference's SDFContactHandler
 // (sdf_physics/physics/contacts.py:31-141) for a batch of body pairs, with its vector-Jacobian product.  Exported by
-// libdiffsdfsim_hip.so beside the functions of include/diffsdfsim_hip.h, whose conventions it shares (device pointers into
+// libdiffsdfsim_hip.so beside the functions of diffsdfsim_hip.h, whose conventions it shares (device pointers into
 // caller-owned memory, double = binary64 row-major, int = int32, stream = hipStream_t as void*, DSS_E_* return codes).
-// Bound by world_abi.OPTIONAL_PROTOTYPES; diffsdfsim_amd/physics2d/sdf_contacts.py raises if the library does not export it.
+// Part of the checked ABI: bound by world_abi.PROTOTYPES, which tests/test_abi.py holds to these declarations.
 #pragma once
 
 #ifdef __cplusplus

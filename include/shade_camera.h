@@ -1,6 +1,6 @@
 // shade_camera.h -- C ABI of the colour camera (csrc/shade_camera.hip), exported by libdiffsdfsim_hip.so beside the depth
-// camera's (depth_camera.h), whose conventions it shares.  Bound by world_abi.OPTIONAL_PROTOTYPES;
-// diffsdfsim_amd/depth_camera.py raises if the library does not export it.
+// camera's (depth_camera.h), whose conventions it shares.  Part of the checked ABI: bound by world_abi.PROTOTYPES, which
+// tests/test_abi.py holds to these declarations.
 #pragma once
 #include <stddef.h>
 

@@ -1,5 +1,5 @@
 """Test reference (numpy, test infrastructure): the point-cloud loss of voxel-grid segments and its gradient with respect to the
-samples, point by point in float64 (csrc/pointcloud_loss.h: dss_pointcloud_loss_grids' value, dss_pointcloud_loss_grids_adjoint).
+samples, point by point in float64 (include/pointcloud_loss.h: dss_pointcloud_loss_grids' value, dss_pointcloud_loss_grids_adjoint).
 
     u = R(q)^T (x - pos) / scale          R normalised by 2 / (q.q); the point counts iff all |R^T (x - pos)| <= scale
     phi = scale * sum_c w_c(u) s[c]       the 8 corners of the cell of index position (u + 1)/2 (n - 1), clamped to [0, n - 2]

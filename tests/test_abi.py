@@ -77,7 +77,7 @@ def test_library_exports_every_declared_symbol():
 def test_prototype_table_follows_the_header():
     from diffsdfsim_amd import world_abi
     protos = header_prototypes()
-    assert sorted(protos) == declared_symbols() and len(protos) == 31
+    assert sorted(protos) == declared_symbols() and len(protos) == 53
     assert sorted(world_abi.PROTOTYPES) == sorted(protos)
     for name, sig in protos.items():
         assert world_abi.PROTOTYPES[name] == sig, name
@@ -95,6 +95,13 @@ def test_constants_follow_the_header():
     for name in shapes:
         assert getattr(world_abi, name[4:]) == d[name], name
     assert sorted(n for n in vars(world_abi) if n.startswith("SHAPE_")) == [n[4:] for n in shapes]
+    # the headers beside diffsdfsim_hip.h
+    from diffsdfsim_amd import chamfer, grids, pointcloud
+    for name in ("CIRCLE", "RECT", "BOWL", "GRID", "MAXCAND", "OVER_CAP", "OVER_CAND", "MALFORMED"):
+        assert getattr(world_abi, "SDF2D_" + name) == d["DSS_SDF2D_" + name], name
+    assert pointcloud.OUT_IGR == d["DSS_PC_IGR_OUT"]
+    assert grids.BLOCK == d["DSS_GRID_BLOCK"]
+    assert (chamfer.TILE, chamfer.QUERIES) == (d["DSS_CHAMFER_TILE"], d["DSS_CHAMFER_QUERIES"])
 
 
 def test_struct_mirrors_follow_the_header():
@@ -103,6 +110,33 @@ def test_struct_mirrors_follow_the_header():
     assert struct_fields("DssWorld") == [n for n, _ in world_abi.FIELDS]
     assert struct_fields("DssAdjoint") == [n for n, _ in world_abi.ADJ_FIELDS]
     assert struct_fields("DssIgrNet") == [n for n, _ in world_abi.DssIgrNet._fields_] == list(world_abi.IGR_NET_FIELDS)
+    assert struct_fields("DssSdf2dGrids") == [n for n, _ in world_abi.DssSdf2dGrids._fields_] == ["ngrids"] + list(world_abi.SDF2D_GRID_FIELDS)
+
+
+class _Lacking:
+    """Stands in for a loaded library: every function of world_abi.PROTOTYPES but one, as plain attributes."""
+
+    def __init__(self, lacking):
+        from diffsdfsim_amd import world_abi
+        for name in world_abi.PROTOTYPES:
+            if name != lacking:
+                setattr(self, name, lambda *a: 0)
+
+
+def test_bind_raises_on_a_missing_declared_function():
+    import pytest
+    from diffsdfsim_amd import world_abi
+    assert world_abi.bind(_Lacking(None)).dss_shade_render.argtypes is not None      # (complete, and without the optional ones: binds)
+    with pytest.raises(AttributeError, match=r"\bdss_shade_render\b"):
+        world_abi.bind(_Lacking("dss_shade_render"))
+
+
+def test_loader_names_the_missing_function():
+    import pytest
+    from diffsdfsim_amd import _lib
+    assert isinstance(_lib.bind_or_raise(_Lacking(None)), _Lacking)
+    with pytest.raises(_lib.HipLibraryError, match=r"does not export .*\bdss_chamfer_nn\b.*rebuild it"):
+        _lib.bind_or_raise(_Lacking("dss_chamfer_nn"))
 
 
 def test_product_path_refuses_cpu_tensors():

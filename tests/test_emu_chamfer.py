@@ -2,7 +2,7 @@
 the merge of its partials as on the device) against the numpy reference of tests/chamfer_ref.py, whose docstring derives the
 bounds: idx equal to argmin, d2 within 2^-48 relative, both exact on the integer lattice.
 
-Which path a call takes is the launcher's rule of csrc/chamfer.h, mirrored by chamfer.splits: splits = min(ceil(tiles /
+Which path a call takes is the launcher's rule of include/chamfer.h, mirrored by chamfer.splits: splits = min(ceil(tiles /
 SPLIT_TILES), ceil(TARGET_WG / (nseg * query blocks))).  At these small grids the second term is large, so a call is split --
 partials to the workspace, merge kernel -- exactly when its longest reference segment has more than SPLIT_TILES tiles.
 tests/emu/check_chamfer.cpp walks the same shapes as a program of its own under the address and undefined-behaviour sanitizers."""
@@ -37,7 +37,7 @@ def nearest(q, q_off, r, r_off, fill=-7.0):
 
 
 def test_python_constants_are_the_headers():
-    text = open(os.path.join(HERE, "..", "diffsdfsim_amd", "csrc", "chamfer.h")).read()
+    text = open(os.path.join(HERE, "..", "include", "chamfer.h")).read()
     got = {k: int(v) for k, v in re.findall(r"#define DSS_CHAMFER_(\w+) (\d+)", text)}
     assert got == dict(TILE=chamfer.TILE, QUERIES=chamfer.QUERIES, SPLIT_TILES=chamfer.SPLIT_TILES, TARGET_WG=chamfer.TARGET_WG)
 

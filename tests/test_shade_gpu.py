@@ -134,6 +134,8 @@ def test_a_library_without_the_entry_raises(monkeypatch):
             return getattr(real, name)
     pose, kind, prm, tp, tk, tq, cam, K = _surface_inputs()
     depth, seg = depth_camera.render_depth(tp[:1], tk[:1], tq[:1], cam, *K, size=(16, 16))
-    monkeypatch.setattr(_lib, "lib", lambda: Without())
+    # the loader is where a library is held to the headers: let it load this one
+    monkeypatch.setattr(_lib, "_LIB", None)
+    monkeypatch.setattr(_lib.ctypes, "CDLL", lambda path: Without())
     with pytest.raises(_lib.HipLibraryError, match="dss_shade_render"):
         depth_camera.shade(depth, seg, tp[:1], tk[:1], tq[:1], cam, *K, S.COLORS[:3], [])
