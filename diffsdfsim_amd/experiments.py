@@ -597,7 +597,7 @@ def eikonal_residual(sdf):
 
 def fit_pointcloud_grid(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_pose=None, start_pose=None, res=17, scale=None,
                         max_iter=100, lr=0.02, eik_reg=1e-2, optimize_pose=False, extra_cameras=2, noise=0.0, max_points=None, corner_r=0.2,
-                        seed=0, log=None, observe="vertices", mesh_res=128, **scene):
+                        seed=0, log=None, observe="vertices", mesh_res=128, target_mesh=None, **scene):
     """The first-frame stage of fit_pointcloud for a voxel body (SDFGrid3D's field: res^3 samples over the cube of half side
     `scale`, default 1.5 max(target_rad)).  B scenes; scene s has a target sphere or rounded cube of half size target_rad[s] at
     target_pose[s].  Observations: pointcloud_observations of the start frame (either `observe` mode) from the experiment's camera
@@ -608,6 +608,10 @@ def fit_pointcloud_grid(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), tar
     where the first term is match_pointcloud on the grids (its gradient w.r.t. the samples: dss_pointcloud_loss_grids_adjoint).
     The regulariser is needed: sum phi^2 alone is also least for samples that are all zero.
     There is no trajectory stage -- the stepper has no adjoint for a grid's samples.
+    target_mesh=(verts, faces): the target is instead a closed triangle mesh of the user's (meshes.load_obj), the same in every
+    scene: it is voxelised by SDFGrid3D.from_mesh (65^3 samples, centroid at the target pose's position) and the level-set mesh of
+    that body stands where the sphere's did -- its camera-facing vertices are the observations (observe='vertices' only, which
+    is exact for convex meshes), its vertices the chamfer distance's target; target_rad is then the mesh's largest |coordinate|.
     Returns dict(sdf [B,res,res,res] unit-frame samples, pose, scale, history [dict(iter, loss, data)], loss_start, loss_final,
     chamfer_start, chamfer_final [B]: chamfer distance (chamfer.py) between the marching-cubes mesh of the grid, in the world frame of
     the estimate's pose, and the target's mesh in its own; observations)."""
@@ -615,6 +619,12 @@ def fit_pointcloud_grid(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), tar
     from .grids import GridTable
     T = lambda a: torch.as_tensor(np.asarray(a, np.float64))
     target_rad, start_rad = T(target_rad).reshape(-1), T(start_rad).reshape(-1)
+    if target_mesh is not None:
+        if observe != "vertices":
+            raise ValueError("target_mesh: observe='vertices' (the depth camera of this driver sees primitives only)")
+        from .physics3d.bodies import SDFGrid3D
+        mesh_body = SDFGrid3D.from_mesh((0.0, 0.0, 0.0), *target_mesh, res=65)
+        target_rad = torch.full_like(start_rad, float(np.abs(mesh_body.verts_np).max()))
     B = target_rad.numel()
     scale = float(1.5 * target_rad.max()) if scale is None else float(scale)
     ident = torch.tensor([1.0, 0, 0, 0, 0.0, 5.0, 0.0], dtype=torch.float64).repeat(B, 1)
@@ -623,6 +633,8 @@ def fit_pointcloud_grid(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), tar
     with torch.no_grad():
         wt = bounce_world(target_rad, run_time=0.0, shape=shape, corner_r=corner_r, init_pose=target_pose, res=mesh_res, **scene)
         dev = wt.device
+        if target_mesh is not None:      # (run_time 0: the world is never stepped, only its thrown body's mesh and pose are read)
+            wt.body_meshes = [(mesh_body.verts_np, mesh_body.faces_np)] * B
         tgt_cloud = chamfer_hip.pack([_pose_points(m[0], target_pose[s].numpy()) for s, m in enumerate(wt.body_meshes)], dev)
         pts, off, scene_of = [], [0], []
         for cam in orbit_camera_poses(extra_cameras):      # run_time 0: the start frame alone, one segment per scene and view
@@ -1403,6 +1415,8 @@ def main(argv=None):
                     help="pointcloud, recorded: the fitted body (pointcloud only: igr, a neural body of --net whose latent code is fitted; "
                          "grid, a voxel body of --res samples per axis whose samples are fitted to a sphere seen from three sides)")
     ap.add_argument("--res", type=int, default=33, help="pointcloud --shape grid: samples per axis of the voxel body")
+    ap.add_argument("--mesh", default=None, metavar="FILE.obj",
+                    help="pointcloud --shape grid: fit the samples to this closed triangle mesh (SDFGrid3D.from_mesh) instead of a sphere")
     ap.add_argument("--file", default=None, help="recorded: the recording (real_world_data.pkl, or an .npz with its keys)")
     ap.add_argument("--synthetic", action="store_true", help="recorded: fit recordings made by synthesize_recording instead of --file")
     ap.add_argument("--optimizer", default="GD", choices=["GD", "Adam"])
@@ -1441,7 +1455,11 @@ def main(argv=None):
             print("pointcloud igr [%s]: mean loss %.3e -> %.3e, %d scenes" % (stage, float(h[0]["loss"].mean()), float(h[-1]["loss"].mean()), a.scenes))
     elif a.what == "pointcloud" and a.shape == "grid":
         tgt = 0.5 + r.random(a.scenes); st = tgt + 0.1 + 0.4 * r.random(a.scenes)
-        res = fit_pointcloud_grid("sphere", tgt, st, res=a.res, max_iter=a.iters, log=print, observe=a.observe)
+        mesh = None
+        if a.mesh:      # every scene fits the user's mesh, from start spheres of 0.8 .. 1.2 of its extent
+            mesh = meshes.load_obj(a.mesh)
+            st = np.abs(mesh[0] - mesh[0].mean(0)).max() * (0.8 + 0.4 * r.random(a.scenes))
+        res = fit_pointcloud_grid("sphere", tgt, st, res=a.res, max_iter=a.iters, log=print, observe=a.observe, target_mesh=mesh)
         for s in range(a.scenes):
             print("pointcloud grid scene %d: loss %.3e -> %.3e, chamfer %.3e -> %.3e" %
                   (s, res["loss_start"][s], res["loss_final"][s], res["chamfer_start"][s], res["chamfer_final"][s]))

@@ -193,3 +193,27 @@ def bowl_mesh(r, d, numsegs=32):
     faces = np.concatenate([shell[:, ::-1], shell + n0, rim]).astype(np.int64)
     verts[:, 2] += r / 2
     return verts, faces
+
+
+def load_obj(path):
+    """A Wavefront .obj file's triangles -> (verts [nv,3] float64, faces [nf,3] int64).  Only `v` and `f` lines are read (a
+    vertex's first three numbers; of a face corner `i`, `i/j`, `i/j/k` or `i//k` the vertex number i, 1-based, or negative:
+    counted back from the vertices read so far); a polygon of n corners becomes the fan of n - 2 triangles about its first
+    corner.  Everything else -- normals, texture coordinates, groups, materials, comments -- is skipped."""
+    verts, faces = [], []
+    with open(path) as fh:
+        for no, line in enumerate(fh, 1):
+            w = line.split("#", 1)[0].split()
+            if not w:
+                continue
+            if w[0] == "v":
+                if len(w) < 4:
+                    raise ValueError("%s:%d: a vertex needs three coordinates" % (path, no))
+                verts.append([float(x) for x in w[1:4]])
+            elif w[0] == "f":
+                idx = [int(c.split("/", 1)[0]) for c in w[1:]]
+                if len(idx) < 3 or any(i == 0 or i > len(verts) or -i > len(verts) for i in idx):
+                    raise ValueError("%s:%d: a face needs three corners or more, each a vertex read before it" % (path, no))
+                idx = [i - 1 if i > 0 else len(verts) + i for i in idx]
+                faces += [[idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1)]
+    return np.asarray(verts, np.float64).reshape(-1, 3), np.asarray(faces, np.int64).reshape(-1, 3)

@@ -367,6 +367,27 @@ class SDFGrid3D(Body3D):
         self.vgrad_np = np.zeros_like(self.verts_np)
         super().__init__(pos, vel, mass, restitution, fric_coeff, eps, **kw)
 
+    @classmethod
+    def from_mesh(cls, pos, verts, faces, res=64, scale=None, recenter=True, **kw):
+        """The voxel body of a closed triangle mesh (verts [nv,3], faces [nf,3]; numpy arrays or tensors, as meshes.load_obj
+        returns them): res^3 samples of the mesh's exact signed distance over the cube of half side `scale`, computed on the
+        device (mesh_grid.mesh_grid_sdf), then this class's constructor with **kw.  The mesh is validated first
+        (mesh_grid.check_mesh: closed, consistently oriented, non-zero volume; inward faces are flipped).
+        recenter=True moves the mesh's volume centroid to the body's origin, so `pos` is the centre of mass; scale=None takes
+        1.25 max |coordinate|.  The surface has to keep a full cell from the cube's faces, max |coordinate| <= scale (1 - 2 / (res
+        - 1)): ValueError otherwise (with the default scale: res < 11)."""
+        from .. import mesh_grid
+        v, f = mesh_grid.check_mesh(verts, faces)
+        if recenter:
+            v = v - mesh_grid.centroid(v, f)
+        ext, res = float(np.abs(v).max()), int(res)
+        scale = 1.25 * ext if scale is None else float(scale)
+        if res < 3 or not ext <= scale * (1.0 - 2.0 / (res - 1)):
+            raise ValueError("from_mesh: the mesh reaches |coordinate| %g, the cube of half side %g with %d samples per axis holds %g "
+                             "(one cell inside its faces): raise scale or res" % (ext, scale, res, scale * (1.0 - 2.0 / max(res - 1, 1))))
+        sdf = mesh_grid.mesh_grid_sdf([v], [f], (res, res, res), scale, check=False)[0]
+        return cls(pos, scale, sdf.cpu(), **kw)
+
     verts = property(lambda self: torch.as_tensor(self.verts_np))
     faces = property(lambda self: torch.as_tensor(self.faces_np))
 

@@ -60,8 +60,10 @@ PROTOTYPES = {
     "dss_sdf2d_contacts_backward_grids": ("i", "iippppppppppppppppp"),
 }
 # outside the headers, bound where a library exports them: the diagnostic build (csrc/diag_stamps.h, csrc/diag_latency.hip)
-# and the CPU emulator's test hooks (tests/emu/lcp_dense_wave.cpp)
+# and the CPU emulator's test hooks (tests/emu/lcp_dense_wave.cpp); the mesh voxeliser, whose header lies beside its kernel
+# (csrc/mesh_grid.h)
 OPTIONAL_PROTOTYPES = {
+    "dss_mesh_grid_sdf": ("i", "ipppppppiippp"),
     "dss_diag_set_lcp_stamps": ("v", "pp"), "dss_diag_set_np_stamps": ("v", "pp"), "dss_diag_latency": ("v", "iiippppp"),
     "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"], "dss_emu_lcp_dense_group_fits": ("i", "iii"),
 }
