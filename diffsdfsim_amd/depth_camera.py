@@ -13,6 +13,12 @@ depth [nview,H,W] float64 is the distance along the optical axis (0: nothing hit
 body hit (-1 none, -2 the trace ran out of iterations).  Boxes, spheres, cylinders and rounded boxes only: any other shape
 raises.  Device tensors only.  Not differentiable: observations are data.
 
+    depth, seg = render_depth_diff(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size, znear, zfar, grids=None, grid_id=None)
+
+is the same render (the same bits) whose `depth` carries a graph to `pose`, `prm[..., :3]` and, through a GridTable made of grids
+that require grad, to their samples, by the adjoint kernel of csrc/depth_adjoint.hip (ABI: csrc/depth_adjoint.h).  It is the
+derivative of the visible surface at fixed visibility: the motion of silhouettes is not modelled.
+
 Voxel-grid bodies: `grids=` a grids.GridTable (or a list of [n0,n1,n2] arrays) and `grid_id` [nview,nbody] (-1: none) let bodies of
 shape type 7 (SDFGrid3D) and 6 (a neural SDF3D, seen through the value grid its mesh is extracted from: body_grid) into the
 same images, by dss_depth_render_grids; brick, bowl and a grid or neural body without a grid still raise.
@@ -265,3 +271,80 @@ def body_grid(body):
         lat = body.latent.detach().to(torch.float64).to(dev)
         return igr.igr_values(meshsdf._grid_cached(res, dev), lat, body.igr.packed).reshape(res, res, res), float(body.scale.detach())
     raise TypeError("body_grid: an SDFGrid3D or a neural SDF3D, got %s" % type(body).__name__)
+
+
+class _RenderDepth(torch.autograd.Function):
+    """render_depth with a backward by dss_depth_adjoint.  grid_data is grids.data where the table carries a graph, else None."""
+
+    @staticmethod
+    def forward(ctx, pose, prm, grid_data, types, cam, intr, size, znear, zfar, grids, ids, min_cos, dropped_out):
+        pose_c, prm_c = pose.detach().contiguous(), prm.detach().contiguous()
+        depth, seg = render_depth(pose_c, types, prm_c, cam, *intr, size, znear, zfar, grids, ids)
+        ctx.save_for_backward(pose_c, prm_c, types, cam, depth, seg, *(() if grids is None else (ids, grids.off, grids.dims, grids.data.detach())))
+        ctx.intr, ctx.size, ctx.min_cos, ctx.ngrid, ctx.dropped_out = intr, size, float(min_cos), 0 if grids is None else grids.ngrid, dropped_out
+        ctx.mark_non_differentiable(seg)
+        return depth, seg
+
+    @staticmethod
+    def backward(ctx, g_depth, _g_seg):
+        pose, prm, types, cam, depth, seg, *gt = ctx.saved_tensors
+        fn = getattr(_lib.lib(), "dss_depth_adjoint", None)
+        if fn is None:
+            raise _lib.HipLibraryError("the library does not export dss_depth_adjoint: rebuild it (python __graft_entry__.py build)")
+        nview, nbody = pose.shape[:2]
+        (W, H), dev = ctx.size, pose.device
+        g_depth = g_depth.detach().to(torch.float64).contiguous()
+        g_pose = torch.zeros(nview, nbody, 7, dtype=torch.float64, device=dev)
+        g_prm = torch.zeros(nview, nbody, 4, dtype=torch.float64, device=dev)      # (the corner radius is a constant: column 3 stays 0)
+        g3 = torch.zeros(nview, nbody, 3, dtype=torch.float64, device=dev)
+        dropped = torch.zeros(nview, nbody, dtype=torch.int32, device=dev)
+        nbytes = _lib.lib().dss_depth_adjoint_workspace_bytes(nview, nbody, W, H)
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+        g_grid = None
+        if gt:
+            ids, off, dims, data = gt
+            if ctx.needs_input_grad[2]:
+                g_grid = torch.zeros_like(data)
+            gargs = (_lib.ptr(ids), ctx.ngrid, _lib.ptr(off), _lib.ptr(dims), _lib.ptr(data))
+        else:
+            gargs = (None, 0, None, None, None)
+        rc = fn(nview, nbody, _lib.ptr(pose), _lib.ptr(types), _lib.ptr(prm), _lib.ptr(cam), *ctx.intr, W, H, _lib.ptr(depth), _lib.ptr(seg),
+                _lib.ptr(g_depth), ctx.min_cos, *gargs, _lib.ptr(g_pose), _lib.ptr(g3), None if g_grid is None else _lib.ptr(g_grid),
+                _lib.ptr(dropped), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+        _lib.check(rc, "dss_depth_adjoint")
+        g_prm[..., :3] = g3
+        if ctx.dropped_out is not None:
+            ctx.dropped_out.copy_(dropped)
+        return g_pose, g_prm, g_grid, None, None, None, None, None, None, None, None, None, None
+
+
+def render_depth_diff(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640, 480), znear=0.1, zfar=100.0, grids=None, grid_id=None,
+                      min_cos=1e-3, return_dropped=False):
+    """render_depth whose depth is differentiable -> (depth [nview,H,W], seg [nview,H,W]) with the bits of render_depth.
+    `depth` carries a graph to `pose` [nview,nbody,7] (raw quaternion and position), to `prm[..., :3]` (the corner radius prm[..., 3],
+    which is also a grid body's scale, is a constant) and, where `grids` is a grids.GridTable made of tensors that require grad, to
+    those grids' samples (fp64 atomic adds: their gradient is reproducible to rounding, the others bit for bit).
+    d depth / d theta = -(d F / d theta) / (n . d) at every hit pixel (csrc/depth_adjoint.h): the derivative of the visible surface
+    at fixed visibility.  The motion of a silhouette -- a pixel that changes the body it shows -- is NOT modelled, and neither are
+    the camera pose, a body's scale, or the chain from a neural body's value grid to its latent code.  Pixels that hit nothing, and
+    hit pixels whose cosine of incidence is below `min_cos`, contribute nothing; the latter are counted per (view, body).
+    return_dropped: also return an int32 [nview,nbody] tensor that every backward pass through this render fills with those counts."""
+    _lib.require_device(pose, prm)
+    if not 0.0 <= float(min_cos) <= 1.0:
+        raise ValueError("min_cos in [0, 1], got %r" % (min_cos,))
+    dev = pose.device
+    nview, nbody = pose.shape[:2]
+    W, H = int(size[0]), int(size[1])
+    types = torch.as_tensor(shape_type).to(dev, torch.int32).reshape(nview, nbody).contiguous()
+    table, ids = None, None
+    if grids is not None:
+        from .grids import as_table
+        table = as_table(grids, dev)
+        if grid_id is None:
+            raise ValueError("grids= needs grid_id [nview,nbody] (-1: the body has no grid)")
+        ids = table.ids(grid_id, (nview, nbody), dev)
+    data = table.data if table is not None and table.data.requires_grad else None
+    dropped = torch.zeros(nview, nbody, dtype=torch.int32, device=dev) if return_dropped else None
+    depth, seg = _RenderDepth.apply(pose, prm, data, types, _camera(cam_pose, dev), _intrinsics(fx, fy, cx, cy), (W, H), float(znear), float(zfar),
+                                    table, ids, float(min_cos), dropped)
+    return (depth, seg, dropped) if return_dropped else (depth, seg)

@@ -693,6 +693,137 @@ def fit_pointcloud_grid(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), tar
                 target_rad=target_rad.numpy(), target_pose=target_pose.numpy(), observations=obs)
 
 
+# ---- fitting to depth images through the differentiable depth camera (depth_camera.render_depth_diff) ---------------------------
+def depth_residual_loss(depth, seg, obs_depth, obs_seg, body):
+    """The mean squared depth difference over the pixels where both images show body index `body`, per view: [nview] (0 for a view
+    without such a pixel).  depth, seg: a render of the estimate (render_depth_diff: the graph runs through `depth`); obs_depth,
+    obs_seg: the observation.  The residual acts on the surface the estimate presents to the camera; where only one of the two
+    images shows the body nothing pulls (the camera's derivative does not model silhouettes)."""
+    both = ((seg == body) & (obs_seg == body)).to(depth.dtype)
+    return (both * (depth - obs_depth.detach()) ** 2).sum(dim=(1, 2)) / both.sum(dim=(1, 2)).clamp_min(1.0)
+
+
+def _sample_sdf(shape, rad, corner_r, res, scale):
+    """Unit-frame samples [res]^3 of a sphere of radius rad or a rounded cube of half size rad over the cube of half side scale."""
+    g = torch.linspace(-1.0, 1.0, res, dtype=torch.float64) * scale
+    p = torch.stack(torch.meshgrid(g, g, g, indexing="ij"), 3)
+    if shape == "sphere":
+        return (p.norm(dim=3) - rad) / scale
+    q = p.abs() - (rad - corner_r)
+    return (q.clamp_min(0.0).norm(dim=3) + q.max(dim=3).values.clamp_max(0.0) - corner_r) / scale
+
+
+def fit_depth(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_pose=None, start_pose=None, res=17, scale=None, max_iter=100,
+              lr=None, optimizer="Adam", eik_reg=1e-2, extra_cameras=2, size=(80, 60), corner_r=0.2, mesh_res=33, min_cos=1e-3, log=None):
+    """A first-frame fit to depth images, the counterpart of the first stage of fit_pointcloud / fit_pointcloud_grid with a residual
+    between a rendered and an observed depth image in place of the point-cloud loss.  B scenes at once; scene s shows the
+    experiment's floor and wall and a target sphere (or rounded cube, shape="cube") of half size target_rad[s] at target_pose[s],
+    seen by the experiment's camera and `extra_cameras` more (orbit_camera_poses) at `size` pixels with the experiment's field of
+    view.  One view per (scene, camera).
+    shape "sphere" / "cube": the pose and the half size are fitted from start_pose / start_rad.  shape "grid": a voxel body of
+    res^3 samples over the cube of half side `scale` (default 1.5 max target_rad) at the target's pose, started as a sphere of
+    radius start_rad[s]; the samples are fitted (to a target sphere), with eik_reg * eikonal_residual as in fit_pointcloud_grid.
+    loss[s] = the mean over the scene's views of depth_residual_loss of the thrown body.  optimizer: "GD" or "Adam".
+    Chamfer distances (chamfer.py) are between the level-set meshes (marching cubes at mesh_res, or of the fitted grid) of the
+    estimate and of the target, each in its world frame.
+    Returns dict(rad, pose, sdf (grid only), history [dict(iter, loss)], loss_start, loss_final, chamfer_start, chamfer_final [B],
+    dropped [views,3] of the last backward pass)."""
+    from . import depth_camera, meshsdf
+    from .grids import GridTable
+    T = lambda a: torch.as_tensor(np.asarray(a, np.float64))
+    target_rad, start_rad = T(target_rad).reshape(-1), T(start_rad).reshape(-1)
+    B, dev = target_rad.numel(), torch.device("cuda")
+    grid = shape == "grid"
+    ident = torch.tensor([1.0, 0, 0, 0, 0.0, 5.0, 0.0], dtype=torch.float64).repeat(B, 1)
+    target_pose = ident.clone() if target_pose is None else T(target_pose).reshape(B, 7)
+    start_pose = target_pose.clone() if start_pose is None or grid else T(start_pose).reshape(B, 7)
+    scale = float(1.5 * target_rad.max()) if scale is None else float(scale)
+    W, H = int(size[0]), int(size[1])
+    intr = (515.0 * W / 640.0, 515.0 * W / 640.0, W / 2.0 - 0.5, H / 2.0 - 0.5)
+    cams = orbit_camera_poses(extra_cameras)
+    kind = abi.SHAPE_SPHERE if shape in ("sphere", "grid") else abi.SHAPE_BOX_ROUNDED
+    floor = torch.tensor([1.0, 0, 0, 0, 0.0, -0.5, 0.0], dtype=torch.float64)
+    wall = torch.tensor([1.0, 0, 0, 0, 5.0, 5.0, 0.0], dtype=torch.float64)
+    fixed_prm = torch.tensor([[20.0, 1.0, 20.0, 0.0], [1.0, 10.0, 10.0, 0.0]], dtype=torch.float64, device=dev)
+
+    def scene(pose, rad, est):
+        """-> pose [B,3,7], types [B,3], prm [B,3,4] of floor, wall and the thrown body (est and grid: a voxel body)."""
+        ps = torch.stack([floor.to(dev).expand(B, 7), wall.to(dev).expand(B, 7), pose.to(dev)], 1)
+        if est and grid:
+            body = torch.tensor([0.0, 0.0, 0.0, scale], dtype=torch.float64, device=dev).expand(B, 4)
+            types = [abi.SHAPE_BOX, abi.SHAPE_BOX, abi.SHAPE_GRID]
+        else:
+            r = rad.to(dev)
+            z = torch.zeros_like(r)
+            body = torch.stack([r, z, z, z], 1) if kind == abi.SHAPE_SPHERE else torch.stack([2 * r, 2 * r, 2 * r, z + corner_r], 1)
+            types = [abi.SHAPE_BOX, abi.SHAPE_BOX, kind]
+        return ps, torch.tensor(types, dtype=torch.int32).repeat(B, 1), torch.cat([fixed_prm.expand(B, 2, 4), body[:, None]], 1)
+
+    with torch.no_grad():
+        tp, tt, tq = scene(target_pose, target_rad, False)
+        obs = [depth_camera.render_depth(tp, tt, tq, cam, *intr, size=(W, H)) for cam in cams]
+        tshape = "sphere" if kind == abi.SHAPE_SPHERE else "cube"
+        tgt = []
+        for s in range(B):
+            sc_t = 1.5 * float(target_rad[s])
+            v, _ = meshsdf.marching_cubes(_sample_sdf(tshape, float(target_rad[s]), corner_r, mesh_res, sc_t).to(dev), 0.0)
+            tgt.append(_pose_points((v.cpu().numpy() / (mesh_res - 1) * 2.0 - 1.0) * sc_t, target_pose[s].numpy()))
+        tgt_cloud = chamfer_hip.pack(tgt, dev)
+    rot, pos = start_pose[:, :4].clone().requires_grad_(not grid), start_pose[:, 4:].clone().requires_grad_(not grid)
+    rad = start_rad.clone().requires_grad_(not grid)
+    sdf = torch.stack([_sample_sdf("sphere", float(r), corner_r, res, scale) for r in start_rad]).to(dev).requires_grad_() if grid else None
+    params = [sdf] if grid else [rot, pos, rad]
+    lr = (0.02 if grid else 0.05) if lr is None else lr
+    opt = torch.optim.Adam(params, lr=lr) if optimizer == "Adam" else torch.optim.SGD(params, lr=lr)
+    gid = torch.tensor([-1, -1, 0], dtype=torch.int32).repeat(B, 1) + torch.tensor([0, 0, 1], dtype=torch.int32) * torch.arange(B, dtype=torch.int32)[:, None]
+    last = {}
+
+    def losses():
+        ps, ty, pq = scene(torch.cat([rot, pos], 1), rad, True)
+        table = GridTable(list(sdf), dev) if grid else None
+        tot = 0.0
+        for cam, (od, os_) in zip(cams, obs):
+            d, sg, dr = depth_camera.render_depth_diff(ps, ty, pq, cam, *intr, size=(W, H), grids=table, grid_id=gid if grid else None,
+                                                       min_cos=min_cos, return_dropped=True)
+            tot = tot + depth_residual_loss(d, sg, od, os_, 2)
+            last["dropped"] = dr
+        data = tot / len(cams)
+        return (data + eik_reg * eikonal_residual(sdf), data) if grid else (data, data)
+
+    def chamfer_now():
+        with torch.no_grad():
+            pose0, verts = torch.cat([rot, pos], 1).detach().numpy(), []
+            for s in range(B):
+                if grid:
+                    field, n, sc_e = sdf[s].detach(), res, scale
+                else:
+                    sc_e = 1.5 * float(rad[s])
+                    field, n = _sample_sdf(tshape, float(rad[s]), corner_r, mesh_res, sc_e).to(dev), mesh_res
+                v, _ = meshsdf.marching_cubes(field, 0.0)
+                verts.append(_pose_points((v.cpu().numpy() / (n - 1) * 2.0 - 1.0) * sc_e, pose0[s]))
+            return _chamfer_series(verts, tgt_cloud)
+
+    chamfer_start, hist = chamfer_now(), []
+    for e in range(max_iter + 1):      # (the last pass only evaluates)
+        opt.zero_grad()
+        loss, data = losses()
+        hist.append(dict(iter=e, loss=loss.detach().cpu().numpy().copy(), data=data.detach().cpu().numpy().copy()))
+        if log:
+            log("[depth %s] iter %3d  mean loss %.3e  (depth %.3e)" % (shape, e, float(hist[-1]["loss"].mean()), float(hist[-1]["data"].mean())))
+        if e == max_iter:
+            break
+        loss.sum().backward()
+        opt.step()
+        with torch.no_grad():
+            if not grid:
+                rot /= rot.norm(dim=1, keepdim=True)
+                rad.clamp_(min=0.05)
+    return dict(rad=rad.detach().numpy().copy(), pose=torch.cat([rot, pos], 1).detach().numpy().copy(), scale=scale,
+                sdf=None if sdf is None else sdf.detach().cpu().numpy().copy(), history=hist, loss_start=hist[0]["data"], loss_final=hist[-1]["data"],
+                chamfer_start=chamfer_start, chamfer_final=chamfer_now(), target_rad=target_rad.numpy(), target_pose=target_pose.numpy(),
+                dropped=None if "dropped" not in last else last["dropped"].cpu().numpy())
+
+
 # ---- trajectory fitting to recorded RGB-D sequences (trajectory_fitting/optim_pointcloud_real.py) ----------------------------
 PLANE_DIMS = (1.5, 1.0, 1.5)      # :104
 BALL_MASS = 0.058                 # :135
@@ -1410,7 +1541,7 @@ def export_trajectory(path, pose, vel, **meta):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="batched experiment drivers (trajectory_fitting/optim_sphere, inertia_fitting/optim_shapespace and optim_primitives, system_identification/optim_sysid)")
-    ap.add_argument("what", choices=["sphere", "shapespace", "inertia", "primitives", "sysid", "pointcloud", "recorded"])
+    ap.add_argument("what", choices=["sphere", "shapespace", "inertia", "primitives", "sysid", "pointcloud", "recorded", "depth"])
     ap.add_argument("--shape", default="sphere", choices=["sphere", "cube", "igr", "grid"],
                     help="pointcloud, recorded: the fitted body (pointcloud only: igr, a neural body of --net whose latent code is fitted; "
                          "grid, a voxel body of --res samples per axis whose samples are fitted to a sphere seen from three sides)")
@@ -1476,6 +1607,15 @@ def main(argv=None):
         print("pointcloud %s: mean |rad - rad*| %.4f -> %.4f, mean |pos - pos*| %.4f -> %.4f, %d scenes" %
               (a.shape, np.abs(st - tgt).mean(), np.abs(res["rad"] - tgt).mean(), np.linalg.norm(sp[:, 4:] - tp[:, 4:], axis=1).mean(),
                np.linalg.norm(res["pose"][:, 4:] - tp[:, 4:], axis=1).mean(), a.scenes))
+    elif a.what == "depth":
+        # a first-frame fit to depth images through the differentiable depth camera (fit_depth): half sizes as in `pointcloud`
+        if a.shape == "igr":
+            ap.error("depth: --shape sphere, cube or grid")
+        tgt = 0.5 + r.random(a.scenes); st = tgt + 0.1 + 0.4 * r.random(a.scenes)
+        res = fit_depth(a.shape, tgt, st, res=a.res, max_iter=a.iters, optimizer="Adam" if a.shape == "grid" else a.optimizer, log=print)
+        for s in range(a.scenes):
+            print("depth %s scene %d: loss %.3e -> %.3e, chamfer %.3e -> %.3e" %
+                  (a.shape, s, res["loss_start"][s], res["loss_final"][s], res["chamfer_start"][s], res["chamfer_final"][s]))
     elif a.what == "recorded":
         if a.shape in ("igr", "grid"):
             ap.error("recorded: --shape sphere or cube")
