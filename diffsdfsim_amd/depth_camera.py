@@ -16,7 +16,8 @@ raises.  Device tensors only.  Not differentiable: observations are data.
     depth, seg = render_depth_diff(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size, znear, zfar, grids=None, grid_id=None)
 
 is the same render (the same bits) whose `depth` carries a graph to `pose`, `prm[..., :3]` and, through a GridTable made of grids
-that require grad, to their samples, by the adjoint kernel of csrc/depth_adjoint.hip (ABI: csrc/depth_adjoint.h).  It is the
+that require grad, to their samples, by the adjoint kernel of csrc/depth_adjoint.hip (ABI: csrc/depth_adjoint.h), and
+from the samples of a neural body's value grid (igr.igr_lattice_values, body_grid(body, diff=True)) on to its latent code.  It is the
 derivative of the visible surface at fixed visibility: the motion of silhouettes is not modelled.
 
 Voxel-grid bodies: `grids=` a grids.GridTable (or a list of [n0,n1,n2] arrays) and `grid_id` [nview,nbody] (-1: none) let bodies of
@@ -257,10 +258,12 @@ def render_color(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, colors, lights
     return tuple(torch.cat([o[i] for o in out]) for i in range(3))
 
 
-def body_grid(body):
+def body_grid(body, diff=False):
     """The grid through which the camera sees a level-set body -> (samples [n0,n1,n2] float64, scale).  SDFGrid3D: its own `sdf`.
     A neural SDF3D: the network's values on the res^3 lattice its mesh was extracted from (the same lattice and the same
-    igr.igr_values call as meshsdf.igr_mesh), so the camera shows the surface that marching cubes meshed."""
+    igr.igr_values call as meshsdf.igr_mesh), so the camera shows the surface that marching cubes meshed.
+    diff=True: the same samples (the same bits) with the graph to `body.latent` (igr.igr_lattice_values), so that a
+    render_depth_diff of a table made of them reaches the latent code; an SDFGrid3D's `sdf` carries its own graph either way."""
     from . import igr, meshsdf
     from .physics3d.bodies import SDF3D, SDFGrid3D
     if isinstance(body, SDFGrid3D):
@@ -268,6 +271,8 @@ def body_grid(body):
     if isinstance(body, SDF3D):
         dev = body.igr.packed["W0"].device
         res = int(body.res)
+        if diff:
+            return igr.igr_lattice_values(body.latent.to(torch.float64), body.igr.packed, res), float(body.scale.detach())
         lat = body.latent.detach().to(torch.float64).to(dev)
         return igr.igr_values(meshsdf._grid_cached(res, dev), lat, body.igr.packed).reshape(res, res, res), float(body.scale.detach())
     raise TypeError("body_grid: an SDFGrid3D or a neural SDF3D, got %s" % type(body).__name__)
@@ -326,7 +331,9 @@ def render_depth_diff(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640
     those grids' samples (fp64 atomic adds: their gradient is reproducible to rounding, the others bit for bit).
     d depth / d theta = -(d F / d theta) / (n . d) at every hit pixel (csrc/depth_adjoint.h): the derivative of the visible surface
     at fixed visibility.  The motion of a silhouette -- a pixel that changes the body it shows -- is NOT modelled, and neither are
-    the camera pose, a body's scale, or the chain from a neural body's value grid to its latent code.  Pixels that hit nothing, and
+    the camera pose or a body's scale.  A neural body's latent code is reached through its value grid: make the table of
+    igr.igr_lattice_values(latent, packed, res) (or body_grid(body, diff=True)), whose backward pass carries the samples' gradient
+    on to the code (csrc/igr_grid_adjoint.h).  Pixels that hit nothing, and
     hit pixels whose cosine of incidence is below `min_cos`, contribute nothing; the latter are counted per (view, body).
     return_dropped: also return an int32 [nview,nbody] tensor that every backward pass through this render fills with those counts."""
     _lib.require_device(pose, prm)

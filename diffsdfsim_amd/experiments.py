@@ -714,7 +714,8 @@ def _sample_sdf(shape, rad, corner_r, res, scale):
 
 
 def fit_depth(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_pose=None, start_pose=None, res=17, scale=None, max_iter=100,
-              lr=None, optimizer="Adam", eik_reg=1e-2, extra_cameras=2, size=(80, 60), corner_r=0.2, mesh_res=33, min_cos=1e-3, log=None):
+              lr=None, optimizer="Adam", eik_reg=1e-2, extra_cameras=2, size=(80, 60), corner_r=0.2, mesh_res=33, min_cos=1e-3, log=None,
+              target_latents=None, start_latents=None, packed=None, latent_reg=1e-4):
     """A first-frame fit to depth images, the counterpart of the first stage of fit_pointcloud / fit_pointcloud_grid with a residual
     between a rendered and an observed depth image in place of the point-cloud loss.  B scenes at once; scene s shows the
     experiment's floor and wall and a target sphere (or rounded cube, shape="cube") of half size target_rad[s] at target_pose[s],
@@ -723,20 +724,33 @@ def fit_depth(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_pose=N
     shape "sphere" / "cube": the pose and the half size are fitted from start_pose / start_rad.  shape "grid": a voxel body of
     res^3 samples over the cube of half side `scale` (default 1.5 max target_rad) at the target's pose, started as a sphere of
     radius start_rad[s]; the samples are fitted (to a target sphere), with eik_reg * eikonal_residual as in fit_pointcloud_grid.
+    shape "igr": the thrown body is a neural body of the network `packed` (igr.pack_weights) and of size `scale` (default 2) at the
+    target's pose, seen through its value grid of res^3 samples (depth_camera.body_grid); the observations are rendered from
+    target_latents [B,L], and the latent code is fitted from start_latents [B,L] (igr.igr_lattice_values carries the samples'
+    gradient on to the code), with latent_reg |latent|^2 added as in fit_pointcloud_latent; target_rad and start_rad are not used.
     loss[s] = the mean over the scene's views of depth_residual_loss of the thrown body.  optimizer: "GD" or "Adam".
     Chamfer distances (chamfer.py) are between the level-set meshes (marching cubes at mesh_res, or of the fitted grid) of the
     estimate and of the target, each in its world frame.
-    Returns dict(rad, pose, sdf (grid only), history [dict(iter, loss)], loss_start, loss_final, chamfer_start, chamfer_final [B],
-    dropped [views,3] of the last backward pass)."""
+    Returns dict(rad, pose, sdf (grid only), latent and target_latents (igr only), history [dict(iter, loss)], loss_start, loss_final,
+    chamfer_start, chamfer_final [B], dropped [views,3] of the last backward pass)."""
     from . import depth_camera, meshsdf
     from .grids import GridTable
     T = lambda a: torch.as_tensor(np.asarray(a, np.float64))
+    grid, neural = shape == "grid", shape == "igr"
+    level = grid or neural      # the estimate is a level-set body seen through a grid
+    if neural:
+        from . import igr
+        if packed is None or target_latents is None or start_latents is None:
+            raise ValueError('fit_depth("igr"): give target_latents, start_latents and packed')
+        nlat = igr.packed_shape(packed)[1]
+        target_lat, start_lat = T(target_latents).reshape(-1, nlat), T(start_latents).reshape(-1, nlat)
+        target_rad = start_rad = torch.ones(target_lat.shape[0], dtype=torch.float64)
+        scale = 2.0 if scale is None else scale
     target_rad, start_rad = T(target_rad).reshape(-1), T(start_rad).reshape(-1)
     B, dev = target_rad.numel(), torch.device("cuda")
-    grid = shape == "grid"
     ident = torch.tensor([1.0, 0, 0, 0, 0.0, 5.0, 0.0], dtype=torch.float64).repeat(B, 1)
     target_pose = ident.clone() if target_pose is None else T(target_pose).reshape(B, 7)
-    start_pose = target_pose.clone() if start_pose is None or grid else T(start_pose).reshape(B, 7)
+    start_pose = target_pose.clone() if start_pose is None or level else T(start_pose).reshape(B, 7)
     scale = float(1.5 * target_rad.max()) if scale is None else float(scale)
     W, H = int(size[0]), int(size[1])
     intr = (515.0 * W / 640.0, 515.0 * W / 640.0, W / 2.0 - 0.5, H / 2.0 - 0.5)
@@ -747,11 +761,11 @@ def fit_depth(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_pose=N
     fixed_prm = torch.tensor([[20.0, 1.0, 20.0, 0.0], [1.0, 10.0, 10.0, 0.0]], dtype=torch.float64, device=dev)
 
     def scene(pose, rad, est):
-        """-> pose [B,3,7], types [B,3], prm [B,3,4] of floor, wall and the thrown body (est and grid: a voxel body)."""
+        """-> pose [B,3,7], types [B,3], prm [B,3,4] of floor, wall and the thrown body (est and grid / igr: a voxel / neural body)."""
         ps = torch.stack([floor.to(dev).expand(B, 7), wall.to(dev).expand(B, 7), pose.to(dev)], 1)
-        if est and grid:
+        if est and level:
             body = torch.tensor([0.0, 0.0, 0.0, scale], dtype=torch.float64, device=dev).expand(B, 4)
-            types = [abi.SHAPE_BOX, abi.SHAPE_BOX, abi.SHAPE_GRID]
+            types = [abi.SHAPE_BOX, abi.SHAPE_BOX, abi.SHAPE_GRID if grid else abi.SHAPE_IGR]
         else:
             r = rad.to(dev)
             z = torch.zeros_like(r)
@@ -759,43 +773,54 @@ def fit_depth(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_pose=N
             types = [abi.SHAPE_BOX, abi.SHAPE_BOX, kind]
         return ps, torch.tensor(types, dtype=torch.int32).repeat(B, 1), torch.cat([fixed_prm.expand(B, 2, 4), body[:, None]], 1)
 
+    gid = torch.tensor([-1, -1, 0], dtype=torch.int32).repeat(B, 1) + torch.tensor([0, 0, 1], dtype=torch.int32) * torch.arange(B, dtype=torch.int32)[:, None]
     with torch.no_grad():
-        tp, tt, tq = scene(target_pose, target_rad, False)
-        obs = [depth_camera.render_depth(tp, tt, tq, cam, *intr, size=(W, H)) for cam in cams]
+        tp, tt, tq = scene(target_pose, target_rad, neural)
+        tvals = igr.igr_lattice_values(target_lat, packed, res) if neural else None
+        ttable = GridTable(list(tvals), dev) if neural else None
+        obs = [depth_camera.render_depth(tp, tt, tq, cam, *intr, size=(W, H), grids=ttable, grid_id=gid if neural else None) for cam in cams]
         tshape = "sphere" if kind == abi.SHAPE_SPHERE else "cube"
         tgt = []
-        for s in range(B):
+        for s in range(B if neural else 0):      # the level set of the target's value grid
+            v, _ = meshsdf.marching_cubes(tvals[s], 0.0)
+            tgt.append(_pose_points((v.cpu().numpy() / (res - 1) * 2.0 - 1.0) * scale, target_pose[s].numpy()))
+        for s in range(0 if neural else B):
             sc_t = 1.5 * float(target_rad[s])
             v, _ = meshsdf.marching_cubes(_sample_sdf(tshape, float(target_rad[s]), corner_r, mesh_res, sc_t).to(dev), 0.0)
             tgt.append(_pose_points((v.cpu().numpy() / (mesh_res - 1) * 2.0 - 1.0) * sc_t, target_pose[s].numpy()))
         tgt_cloud = chamfer_hip.pack(tgt, dev)
-    rot, pos = start_pose[:, :4].clone().requires_grad_(not grid), start_pose[:, 4:].clone().requires_grad_(not grid)
-    rad = start_rad.clone().requires_grad_(not grid)
+    rot, pos = start_pose[:, :4].clone().requires_grad_(not level), start_pose[:, 4:].clone().requires_grad_(not level)
+    rad = start_rad.clone().requires_grad_(not level)
+    lat = start_lat.clone().requires_grad_() if neural else None
     sdf = torch.stack([_sample_sdf("sphere", float(r), corner_r, res, scale) for r in start_rad]).to(dev).requires_grad_() if grid else None
-    params = [sdf] if grid else [rot, pos, rad]
-    lr = (0.02 if grid else 0.05) if lr is None else lr
+    params = [sdf] if grid else [lat] if neural else [rot, pos, rad]
+    lr = (0.02 if grid else 0.01 if neural else 0.05) if lr is None else lr
     opt = torch.optim.Adam(params, lr=lr) if optimizer == "Adam" else torch.optim.SGD(params, lr=lr)
-    gid = torch.tensor([-1, -1, 0], dtype=torch.int32).repeat(B, 1) + torch.tensor([0, 0, 1], dtype=torch.int32) * torch.arange(B, dtype=torch.int32)[:, None]
     last = {}
 
     def losses():
         ps, ty, pq = scene(torch.cat([rot, pos], 1), rad, True)
-        table = GridTable(list(sdf), dev) if grid else None
+        if neural:      # the value grids of all scenes, one network pass forward and one compacted pass backward
+            last["vals"] = igr.igr_lattice_values(lat, packed, res)
+        table = GridTable(list(sdf if grid else last["vals"]), dev) if level else None
         tot = 0.0
         for cam, (od, os_) in zip(cams, obs):
-            d, sg, dr = depth_camera.render_depth_diff(ps, ty, pq, cam, *intr, size=(W, H), grids=table, grid_id=gid if grid else None,
+            d, sg, dr = depth_camera.render_depth_diff(ps, ty, pq, cam, *intr, size=(W, H), grids=table, grid_id=gid if level else None,
                                                        min_cos=min_cos, return_dropped=True)
             tot = tot + depth_residual_loss(d, sg, od, os_, 2)
             last["dropped"] = dr
         data = tot / len(cams)
+        if neural:
+            return data + latent_reg * (lat.to(dev) ** 2).sum(dim=1), data
         return (data + eik_reg * eikonal_residual(sdf), data) if grid else (data, data)
 
     def chamfer_now():
         with torch.no_grad():
             pose0, verts = torch.cat([rot, pos], 1).detach().numpy(), []
+            fields = sdf if grid else igr.igr_lattice_values(lat.detach(), packed, res) if neural else None
             for s in range(B):
-                if grid:
-                    field, n, sc_e = sdf[s].detach(), res, scale
+                if level:
+                    field, n, sc_e = fields[s].detach(), res, scale
                 else:
                     sc_e = 1.5 * float(rad[s])
                     field, n = _sample_sdf(tshape, float(rad[s]), corner_r, mesh_res, sc_e).to(dev), mesh_res
@@ -808,17 +833,21 @@ def fit_depth(shape="sphere", target_rad=(1.0,), start_rad=(1.3,), target_pose=N
         opt.zero_grad()
         loss, data = losses()
         hist.append(dict(iter=e, loss=loss.detach().cpu().numpy().copy(), data=data.detach().cpu().numpy().copy()))
+        if neural:
+            hist[-1]["latent"] = lat.detach().numpy().copy()
         if log:
-            log("[depth %s] iter %3d  mean loss %.3e  (depth %.3e)" % (shape, e, float(hist[-1]["loss"].mean()), float(hist[-1]["data"].mean())))
+            log("[depth %s] iter %3d  mean loss %.3e  (depth %.3e)%s" % (shape, e, float(hist[-1]["loss"].mean()), float(hist[-1]["data"].mean()),
+                "  mean |latent - target| %.4f" % float((lat.detach() - target_lat).abs().mean()) if neural else ""))
         if e == max_iter:
             break
         loss.sum().backward()
         opt.step()
         with torch.no_grad():
-            if not grid:
+            if not level:
                 rot /= rot.norm(dim=1, keepdim=True)
                 rad.clamp_(min=0.05)
-    return dict(rad=rad.detach().numpy().copy(), pose=torch.cat([rot, pos], 1).detach().numpy().copy(), scale=scale,
+    return dict(latent=None if lat is None else lat.detach().numpy().copy(), target_latents=target_lat.numpy() if neural else None,
+                rad=rad.detach().numpy().copy(), pose=torch.cat([rot, pos], 1).detach().numpy().copy(), scale=scale,
                 sdf=None if sdf is None else sdf.detach().cpu().numpy().copy(), history=hist, loss_start=hist[0]["data"], loss_final=hist[-1]["data"],
                 chamfer_start=chamfer_start, chamfer_final=chamfer_now(), target_rad=target_rad.numpy(), target_pose=target_pose.numpy(),
                 dropped=None if "dropped" not in last else last["dropped"].cpu().numpy())
@@ -1543,9 +1572,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description="batched experiment drivers (trajectory_fitting/optim_sphere, inertia_fitting/optim_shapespace and optim_primitives, system_identification/optim_sysid)")
     ap.add_argument("what", choices=["sphere", "shapespace", "inertia", "primitives", "sysid", "pointcloud", "recorded", "depth"])
     ap.add_argument("--shape", default="sphere", choices=["sphere", "cube", "igr", "grid"],
-                    help="pointcloud, recorded: the fitted body (pointcloud only: igr, a neural body of --net whose latent code is fitted; "
+                    help="pointcloud, depth, recorded: the fitted body (pointcloud and depth only: igr, a neural body of --net whose latent code is fitted; "
                          "grid, a voxel body of --res samples per axis whose samples are fitted to a sphere seen from three sides)")
-    ap.add_argument("--res", type=int, default=33, help="pointcloud --shape grid: samples per axis of the voxel body")
+    ap.add_argument("--res", type=int, default=33, help="pointcloud, depth --shape grid: samples per axis of the voxel body; depth --shape igr: of the neural body's value grid")
     ap.add_argument("--mesh", default=None, metavar="FILE.obj",
                     help="pointcloud --shape grid: fit the samples to this closed triangle mesh (SDFGrid3D.from_mesh) instead of a sphere")
     ap.add_argument("--file", default=None, help="recorded: the recording (real_world_data.pkl, or an .npz with its keys)")
@@ -1609,10 +1638,16 @@ def main(argv=None):
                np.linalg.norm(res["pose"][:, 4:] - tp[:, 4:], axis=1).mean(), a.scenes))
     elif a.what == "depth":
         # a first-frame fit to depth images through the differentiable depth camera (fit_depth): half sizes as in `pointcloud`
-        if a.shape == "igr":
-            ap.error("depth: --shape sphere, cube or grid")
-        tgt = 0.5 + r.random(a.scenes); st = tgt + 0.1 + 0.4 * r.random(a.scenes)
-        res = fit_depth(a.shape, tgt, st, res=a.res, max_iter=a.iters, optimizer="Adam" if a.shape == "grid" else a.optimizer, log=print)
+        if a.shape == "igr":      # the latent code of a neural body of --net, as `pointcloud --shape igr` draws it
+            from . import igr
+            width, nlat = igr.SHAPES[a.net == "shapenet"]
+            packed = igr.pack_weights(*scenes.geometric_init_weights(a.seed, 0.5, width, nlat))
+            tl, sl = 0.1 * r.standard_normal((a.scenes, nlat)), 0.1 * r.standard_normal((a.scenes, nlat))
+            res = fit_depth("igr", res=a.res, max_iter=a.iters, optimizer="Adam", log=print, target_latents=tl, start_latents=sl, packed=packed)
+            print("depth igr: mean |latent - target| %.4f -> %.4f" % (np.abs(sl - tl).mean(), np.abs(res["latent"] - tl).mean()))
+        else:
+            tgt = 0.5 + r.random(a.scenes); st = tgt + 0.1 + 0.4 * r.random(a.scenes)
+            res = fit_depth(a.shape, tgt, st, res=a.res, max_iter=a.iters, optimizer="Adam" if a.shape == "grid" else a.optimizer, log=print)
         for s in range(a.scenes):
             print("depth %s scene %d: loss %.3e -> %.3e, chamfer %.3e -> %.3e" %
                   (a.shape, s, res["loss_start"][s], res["loss_final"][s], res["chamfer_start"][s], res["chamfer_final"][s]))

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .world_abi import IGR_NET_POINTERS, DssIgrNet
+from .world_abi import IGR_LATENT_MAX, IGR_NET_POINTERS, DssIgrNet
 
 H = 128                                  # the bob_spot_setup width (dss_igr_query, dss_igr_query_latent_grad)
 SHAPES = ((128, 2), (256, 4))            # (hidden width, latent size) the kernels are instantiated for
@@ -117,6 +117,88 @@ def igr_values(pts, latent, P):
     quarter of the matrix work of `igr_query` (no tangents) -- what sampling the 128^3 grid of a level-set mesh needs
     (bodies.py:657-664)."""
     return igr_query_list(pts, latent, P, MODE_VALUE)
+
+
+def igr_grid_adjoint(g_grid, dims, lat_idx, latents, P, cap=None, return_nodes=False):
+    """The chain from value grids to latent codes (dss_igr_grid_adjoint, csrc/igr_grid_adjoint.h): g_grid, the adjoint of the
+    values of `ngrid` lattices over [-1, 1]^3 pooled one after the other (x slowest, float64 on the device); dims [ngrid,3]; lat_idx
+    [ngrid] the row of `latents` [nlat,L] whose code grid g was sampled with (< 0: not a neural grid, skipped).
+    -> g_latent [nlat,L] = sum over a row's grids and their nodes of g_grid * d f / d latent, bit-reproducible.  Only the
+    non-zero nodes reach the network: `cap` is the capacity of their list (default max(4096, samples // 16)); a list that
+    does not fit costs one more call with the capacity the first one reported.  return_nodes: also the number of nodes."""
+    _lib.require_device(g_grid, latents)
+    fn, size = getattr(_lib.lib(), "dss_igr_grid_adjoint", None), getattr(_lib.lib(), "dss_igr_grid_adjoint_workspace_bytes", None)
+    if fn is None or size is None:
+        raise _lib.HipLibraryError("the library does not export dss_igr_grid_adjoint: rebuild it (python __graft_entry__.py build)")
+    dev = g_grid.device
+    dims = np.asarray(dims, np.int64).reshape(-1, 3)
+    sizes = dims.prod(1)
+    ngrid, nsamples = len(dims), int(sizes.sum())
+    g = g_grid.detach().to(torch.float64).contiguous().reshape(-1)
+    _width, nlat = packed_shape(P)
+    lat = latents.detach().to(torch.float64).reshape(-1, nlat)
+    rows = np.asarray(lat_idx, np.int64).reshape(-1)
+    if g.numel() != nsamples or len(rows) != ngrid or nsamples > 2 ** 31 - 1 or dims.min() < 2 or rows.max() >= lat.shape[0]:
+        raise ValueError("g_grid pools the samples of dims (each >= 2, below 2^31 together) and lat_idx names a row of latents per grid: "
+                         "dims has %d grids of %d samples together, g_grid %d samples, lat_idx %d entries (largest %d), latents %d rows"
+                         % (ngrid, nsamples, g.numel(), len(rows), int(rows.max()) if len(rows) else -1, lat.shape[0]))
+    table = torch.zeros(lat.shape[0], IGR_LATENT_MAX, dtype=torch.float64, device=dev)
+    table[:, :nlat] = lat
+    off = torch.as_tensor(np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int32)).to(dev)
+    dims_d, rows_d = torch.as_tensor(dims.astype(np.int32)).to(dev).contiguous(), torch.as_tensor(rows.astype(np.int32)).to(dev)
+    out = torch.zeros(lat.shape[0], IGR_LATENT_MAX, dtype=torch.float64, device=dev)
+    n_nodes = torch.zeros(1, dtype=torch.int32, device=dev)
+    net = net_struct(P)
+    cap = max(4096, nsamples // 16) if cap is None else int(cap)
+    # the size function bounds the chunks (2048 samples of one grid) by the samples alone, nsamples / 2048 + nsamples / 8 + 1, and the
+    # call checks the workspace against the chunks the tables name: asking for 8 samples per chunk covers those and no more
+    nchunk = int((-(-sizes[rows >= 0] // 2048)).sum())
+    for attempt in (0, 1):
+        nbytes = size(max(min(nsamples, 8 * nchunk), 1), cap, lat.shape[0])
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+        rc = fn(ctypes.byref(net), ngrid, _lib.ptr(off), _lib.ptr(dims_d), _lib.ptr(rows_d), _lib.ptr(table), IGR_LATENT_MAX, lat.shape[0],
+                _lib.ptr(g), cap, _lib.ptr(out), _lib.ptr(n_nodes), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
+        if rc != -2 or attempt or int(n_nodes) <= cap:      # DSS_E_WORKSPACE with n_nodes > cap: the list did not fit
+            break
+        cap = int(n_nodes)
+    _lib.check(rc, "dss_igr_grid_adjoint")
+    return (out[:, :nlat], int(n_nodes)) if return_nodes else out[:, :nlat]
+
+
+class _IgrLatticeValues(torch.autograd.Function):
+    """igr_values on the res^3 lattice (forward: one network launch per row of the batch, so that each grid has igr_values' bits)
+    with a backward by dss_igr_grid_adjoint, one call for all the grids of a batch."""
+
+    @staticmethod
+    def forward(ctx, latent, P, res):
+        from .meshsdf import _grid_cached
+        dev = P["W0"].device
+        lat = latent.detach().to(torch.float64).to(dev).reshape(-1, packed_shape(P)[1])
+        pts = _grid_cached(res, dev)
+        vals = torch.stack([igr_values(pts, row, P).reshape(res, res, res) for row in lat])
+        ctx.save_for_backward(lat)
+        ctx.P, ctx.res, ctx.like = P, res, (latent.shape, latent.device, latent.dtype)
+        return vals if latent.dim() == 2 else vals[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (lat,) = ctx.saved_tensors
+        B, res = lat.shape[0], ctx.res
+        out = igr_grid_adjoint(g.to(lat.device), [[res] * 3] * B, np.arange(B), lat, ctx.P)
+        shape, ldev, dtype = ctx.like
+        return out.reshape(shape).to(ldev, dtype), None, None
+
+
+def igr_lattice_values(latent, P, res):
+    """The network's values on the res^3 lattice of meshsdf._grid(res), differentiable w.r.t. the latent code: latent [L] ->
+    [res,res,res] (the bits of igr_values on that lattice, what depth_camera.body_grid returns), latent [B,L] -> [B,res,res,res].
+    The forward pass is one igr_values launch per code; the backward pass is igr_grid_adjoint: one call for the whole batch, over the nodes whose adjoint is not zero -- a depth
+    image or a point cloud touches a small part of the lattice.  Float64, on the device of the packed network."""
+    latent = torch.as_tensor(latent)
+    nlat = packed_shape(P)[1]
+    if latent.dim() not in (1, 2) or latent.shape[-1] != nlat or int(res) < 2:
+        raise ValueError("latent [%d] or [B,%d] and res >= 2, got %s and %r" % (nlat, nlat, tuple(latent.shape), res))
+    return _IgrLatticeValues.apply(latent, P, int(res))
 
 
 def weights_from_module(network):

@@ -61,10 +61,12 @@ PROTOTYPES = {
 }
 # outside the headers, bound where a library exports them: the diagnostic build (csrc/diag_stamps.h, csrc/diag_latency.hip)
 # and the CPU emulator's test hooks (tests/emu/lcp_dense_wave.cpp); the mesh voxeliser, whose header lies beside its kernel
-# (csrc/mesh_grid.h) and the depth camera's adjoint (csrc/depth_adjoint.h)
+# (csrc/mesh_grid.h), the depth camera's adjoint (csrc/depth_adjoint.h) and the chain from a neural body's value grid to its
+# latent code (csrc/igr_grid_adjoint.h)
 OPTIONAL_PROTOTYPES = {
     "dss_mesh_grid_sdf": ("i", "ipppppppiippp"),
     "dss_depth_adjoint_workspace_bytes": ("z", "iiii"), "dss_depth_adjoint": ("i", "iippppddddiipppdpippppppppzp"),
+    "dss_igr_grid_adjoint_workspace_bytes": ("z", "iii"), "dss_igr_grid_adjoint": ("i", "pippppiipipppzp"),
     "dss_diag_set_lcp_stamps": ("v", "pp"), "dss_diag_set_np_stamps": ("v", "pp"), "dss_diag_latency": ("v", "iiippppp"),
     "dss_emu_lcp_dense_wave_forward": PROTOTYPES["dss_lcp_dense_forward"], "dss_emu_lcp_dense_group_fits": ("i", "iii"),
 }
