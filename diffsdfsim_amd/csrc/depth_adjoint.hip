@@ -16,8 +16,6 @@
 //
 // Grid samples: a lane adds its eight terms with the hardware's fp64 global atomic add (-munsafe-fp-atomics), as
 // pointcloud_loss_grid_adj.hip does; the order of the adds into one sample is the order of arrival.
-#include <vector>
-
 #include "depth_trace.h"
 #include "depth_adjoint.h"
 #include "depth_adjoint_point.h"
@@ -201,17 +199,11 @@ int dss_depth_adjoint(int nview, int nbody, const double *pose, const int *shape
     hipStream_t st = (hipStream_t)stream;
     const size_t ntype = (size_t)nview * nbody;
     const bool table = grid_id != nullptr && ngrid > 0;
-#if defined(DSS_EMU)
-    const int *types = shape_type, *ids = table ? grid_id : nullptr, *dims = grid_dims;      // (the emulator's device memory is the host's)
-#else
-    std::vector<int> host_types(ntype), host_ids(table ? ntype : 0), host_dims(table ? 3 * (size_t)ngrid : 0);
-    if (hipMemcpyAsync(host_types.data(), shape_type, sizeof(int) * ntype, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (table && hipMemcpyAsync(host_ids.data(), grid_id, sizeof(int) * ntype, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        (table && hipMemcpyAsync(host_dims.data(), grid_dims, sizeof(int) * 3 * (size_t)ngrid, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipStreamSynchronize(st) != hipSuccess)
+    HostInts host_types, host_ids, host_dims;
+    if (!host_types.copy(shape_type, ntype, st) || (table && !host_ids.copy(grid_id, ntype, st)) ||
+        (table && !host_dims.copy(grid_dims, 3 * (size_t)ngrid, st)) || !host_sync(st))
         return DSS_E_BADARG;
-    const int *types = host_types.data(), *ids = table ? host_ids.data() : nullptr, *dims = host_dims.data();
-#endif
+    const int *types = host_types.p, *ids = host_ids.p, *dims = host_dims.p;
     if (table)
         for (int g = 0; g < 3 * ngrid; ++g)
             if (dims[g] < 2) return DSS_E_BADARG;

@@ -11,13 +11,12 @@
 //                             of its own, the same per-pixel body compiled with the grid trace in it (dc_pixel<true>); a grid is
 //                             walked cell by cell by a two-level 3-D DDA over the block minima of dss_grid_block_min
 //   dss_grid_block_min        a thread per block of 4 x 4 x 4 cells: the least of its 5 x 5 x 5 corner samples
-//   dss_depth_points_count    a wavefront per image row, 64 columns at a time: ballot of the selected pixels, popcount
-//   dss_depth_points_emit     the same walk; a selected pixel's slot is the row's offset + the popcount of the lanes below it
+//   dss_depth_points_count    the row compaction of chunk_grid.h (a wavefront per image row) over dp_selected
+//   dss_depth_points_emit     the same walk; writes the selected pixels' points in world coordinates
 //
 // fp64 VALU throughout; no atomics, so every output is a function of the input alone.
 // The tables, the ray, the slab test and the traces are those of depth_trace.h, which the colour camera shares.
-#include <vector>
-
+#include "chunk_grid.h"
 #include "depth_trace.h"
 
 namespace {
@@ -116,42 +115,34 @@ __device__ __forceinline__ bool dp_selected(const double *__restrict__ depth, co
     return seg[i] == body && seg[i - 1] == body && seg[i + 1] == body && seg[i - W] == body && seg[i + W] == body && depth[i] != 0.0;
 }
 
-__global__ void __launch_bounds__(DC_THREADS) depth_points_count_kernel(int nrow, int H, int W, int body, const double *__restrict__ depth,
+__global__ void __launch_bounds__(CG_THREADS) depth_points_count_kernel(int nrow, int H, int W, int body, const double *__restrict__ depth,
                                                                        const int *__restrict__ seg, int *__restrict__ row_count)
 {
-    const int g = blockIdx.x * (DC_THREADS / WAVE) + threadIdx.x / WAVE, lane = lane_id();
-    if (g >= nrow) return;      // (the whole wavefront)
+    int g;
+    if (!row_of_wave(nrow, g)) return;
     const int view = g / H, r = g - view * H;
     const size_t base = (size_t)view * H * W;
-    int n = 0;
-    for (int c0 = 0; c0 < W; c0 += WAVE) n += __popcll(__ballot(dp_selected(depth, seg, base, W, H, r, c0 + lane, body)));
-    if (lane == 0) row_count[g] = n;
+    const int n = dss::row_count(W, [&](int c) { return dp_selected(depth, seg, base, W, H, r, c, body); });
+    if (lane_id() == 0) row_count[g] = n;
 }
 
-__global__ void __launch_bounds__(DC_THREADS) depth_points_emit_kernel(int nrow, int H, int W, int body, const double *__restrict__ depth,
+__global__ void __launch_bounds__(CG_THREADS) depth_points_emit_kernel(int nrow, int H, int W, int body, const double *__restrict__ depth,
                                                                       const int *__restrict__ seg, const int *__restrict__ row_off,
                                                                       const double *__restrict__ cam, double fx, double fy, double cx, double cy,
                                                                       double *__restrict__ pts)
 {
-    const int g = blockIdx.x * (DC_THREADS / WAVE) + threadIdx.x / WAVE, lane = lane_id();
-    if (g >= nrow) return;
+    int g;
+    if (!row_of_wave(nrow, g)) return;
     const int view = g / H, r = g - view * H;
     const size_t base = (size_t)view * H * W;
     const double ny = (r + 0.5 - cy) / fy;
-    int at = row_off[g];
-    for (int c0 = 0; c0 < W; c0 += WAVE) {
-        const int c = c0 + lane;
-        const bool sel = dp_selected(depth, seg, base, W, H, r, c, body);
-        const unsigned long long mask = __ballot(sel);
-        if (sel) {
-            const double dz = depth[base + (size_t)r * W + c], nx = (c + 0.5 - cx) / fx;
-            const double x = nx * dz, y = -(ny * dz), z = -dz;      // OpenGL camera frame: y and z flipped
-            double *out = pts + 3 * (size_t)(at + __popcll(mask & ((1ull << lane) - 1ull)));
+    row_emit(W, row_off[g], [&](int c) { return dp_selected(depth, seg, base, W, H, r, c, body); }, [&](int slot, int c) {
+        const double dz = depth[base + (size_t)r * W + c], nx = (c + 0.5 - cx) / fx;
+        const double x = nx * dz, y = -(ny * dz), z = -dz;      // OpenGL camera frame: y and z flipped
+        double *out = pts + 3 * (size_t)slot;
 #pragma unroll
-            for (int i = 0; i < 3; ++i) out[i] = cam[4 * i] * x + cam[4 * i + 1] * y + cam[4 * i + 2] * z + cam[4 * i + 3];
-        }
-        at += __popcll(mask);
-    }
+        for (int i = 0; i < 3; ++i) out[i] = cam[4 * i] * x + cam[4 * i + 1] * y + cam[4 * i + 2] * z + cam[4 * i + 3];
+    });
 }
 
 }  // namespace
@@ -169,15 +160,9 @@ int dss_depth_render(int nview, int nbody, const double *pose, const int *shape_
     // the shape types decide the status, so the host reads them before anything is enqueued
     hipStream_t st = (hipStream_t)stream;
     const size_t ntype = (size_t)nview * nbody;
-#if defined(DSS_EMU)
-    const int *types = shape_type;      // (the emulator's device memory is the host's)
-#else
-    std::vector<int> host_types(ntype);
-    if (hipMemcpyAsync(host_types.data(), shape_type, sizeof(int) * ntype, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return DSS_E_BADARG;
-    const int *types = host_types.data();
-#endif
+    HostInts host_types;
+    if (!host_types.copy(shape_type, ntype, st) || !host_sync(st)) return DSS_E_BADARG;
+    const int *types = host_types.p;
     for (size_t i = 0; i < ntype; ++i)
         if (types[i] != DSS_SHAPE_BOX && types[i] != DSS_SHAPE_SPHERE && types[i] != DSS_SHAPE_CYLINDER && types[i] != DSS_SHAPE_BOX_ROUNDED)
             return DSS_E_UNSUPPORTED;      // brick, bowl: not shown to bound the distance; neural and grid bodies: not in this renderer
@@ -210,17 +195,11 @@ int dss_depth_render_grids(int nview, int nbody, const double *pose, const int *
     // shape types, grid ids and the grids' dims decide the status, so the host reads them before anything is enqueued
     hipStream_t st = (hipStream_t)stream;
     const size_t ntype = (size_t)nview * nbody;
-#if defined(DSS_EMU)
-    const int *types = shape_type, *ids = grid_id, *dims = grid_dims;      // (the emulator's device memory is the host's)
-#else
-    std::vector<int> host_types(ntype), host_ids(ntype), host_dims(3 * (size_t)ngrid);
-    if (hipMemcpyAsync(host_types.data(), shape_type, sizeof(int) * ntype, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(host_ids.data(), grid_id, sizeof(int) * ntype, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (ngrid > 0 && hipMemcpyAsync(host_dims.data(), grid_dims, sizeof(int) * 3 * (size_t)ngrid, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipStreamSynchronize(st) != hipSuccess)
+    HostInts host_types, host_ids, host_dims;
+    if (!host_types.copy(shape_type, ntype, st) || !host_ids.copy(grid_id, ntype, st) ||
+        (ngrid > 0 && !host_dims.copy(grid_dims, 3 * (size_t)ngrid, st)) || !host_sync(st))
         return DSS_E_BADARG;
-    const int *types = host_types.data(), *ids = host_ids.data(), *dims = host_dims.data();
-#endif
+    const int *types = host_types.p, *ids = host_ids.p, *dims = host_dims.p;
     for (int g = 0; g < 3 * ngrid; ++g)
         if (dims[g] < 2) return DSS_E_BADARG;
     bool any = false;
@@ -247,8 +226,8 @@ int dss_depth_points_count(int nview, int H, int W, int body, const double *dept
 {
     if (nview <= 0 || H <= 0 || W <= 0 || !depth || !seg || !row_count) return DSS_E_BADARG;
     if (!dc_images_ok(nview, H, W)) return DSS_E_UNSUPPORTED;
-    const int nrow = nview * H, per = DC_THREADS / WAVE;
-    hipLaunchKernelGGL(depth_points_count_kernel, dim3((nrow + per - 1) / per), dim3(DC_THREADS), 0, (hipStream_t)stream, nrow, H, W, body,
+    const int nrow = nview * H;
+    hipLaunchKernelGGL(depth_points_count_kernel, dim3(row_blocks(nrow)), dim3(CG_THREADS), 0, (hipStream_t)stream, nrow, H, W, body,
                        depth, seg, row_count);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }
@@ -259,8 +238,8 @@ int dss_depth_points_emit(int nview, int H, int W, int body, const double *depth
     // (pts may be NULL: no pixel selected, nothing is written)
     if (nview <= 0 || H <= 0 || W <= 0 || !depth || !seg || !row_off || !cam || !(fx != 0.0) || !(fy != 0.0)) return DSS_E_BADARG;
     if (!dc_images_ok(nview, H, W)) return DSS_E_UNSUPPORTED;
-    const int nrow = nview * H, per = DC_THREADS / WAVE;
-    hipLaunchKernelGGL(depth_points_emit_kernel, dim3((nrow + per - 1) / per), dim3(DC_THREADS), 0, (hipStream_t)stream, nrow, H, W, body,
+    const int nrow = nview * H;
+    hipLaunchKernelGGL(depth_points_emit_kernel, dim3(row_blocks(nrow)), dim3(CG_THREADS), 0, (hipStream_t)stream, nrow, H, W, body,
                        depth, seg, row_off, cam, fx, fy, cx, cy, pts);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }

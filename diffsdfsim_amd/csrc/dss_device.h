@@ -28,6 +28,8 @@ __device__ __forceinline__ double dss_wave_bcast(double x, int src_uniform) { re
 __device__ inline double dss_wave_first(double x) { return __shfl(x, 0, 64); }
 #else
 #include <hip/hip_runtime.h>
+
+#include <vector>
 #define DSS_DYN_LDS(type, name) extern __shared__ __align__(16) type name[]
 // LDS written by one lane is visible to the other lanes of the SAME wavefront afterwards (no s_barrier: the LDS
 // queue of a wavefront is in order; the fence only stops the compiler from moving accesses across)
@@ -77,6 +79,31 @@ template <int J> __device__ __forceinline__ double dss_gbc(double x)
     const double lo = __builtin_amdgcn_update_dpp(x, x, 0x150 + J, 0xf, 0x3, false);          // lanes 8-15 of the row keep x for now
     return __builtin_amdgcn_update_dpp(lo, x, 0x150 + 8 + J, 0xf, 0xc, false);
 }
+#endif
+
+// Ints of device memory that decide a status or a launch shape, read by the host before it enqueues more.  copy() enqueues the
+// read on the stream (false where the runtime refused the pointer); after host_sync(), the call's one wait, p holds the values.
+// The emulator's device memory is the host's: p is the pointer itself and there is nothing to wait for.
+struct HostInts {
+    const int *p = nullptr;      // (stays NULL without a copy)
+#if defined(DSS_EMU)
+    bool copy(const int *dev, size_t, hipStream_t) { p = dev; return true; }
+#else
+    int one;      // (a single int, such as a list's length, needs no allocation)
+    std::vector<int> own;
+    bool copy(const int *dev, size_t n, hipStream_t st)
+    {
+        int *host = &one;
+        if (n > 1) { own.resize(n); host = own.data(); }
+        p = host;
+        return hipMemcpyAsync(host, dev, sizeof(int) * n, hipMemcpyDeviceToHost, st) == hipSuccess;
+    }
+#endif
+};
+#if defined(DSS_EMU)
+inline bool host_sync(hipStream_t) { return true; }
+#else
+inline bool host_sync(hipStream_t st) { return hipStreamSynchronize(st) == hipSuccess; }
 #endif
 
 // A big by-value kernel argument (DssWorld, ~1 KB) whose address is handed to non-inlined device functions is copied by the

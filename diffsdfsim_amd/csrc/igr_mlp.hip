@@ -365,6 +365,11 @@ inline bool net_ok(const DssIgrNet *N) { return N && N->W0 && N->b0 && N->Wp && 
 }  // namespace
 
 namespace dss {
+int igr_net_latent(const DssIgrNet &N)
+{
+    const int kind = net_kind(N);
+    return kind == NET_BOB_SPOT ? NetBobSpot::L : (kind == NET_SHAPENET ? NetShapenet::L : -1);
+}
 // used by the neural narrow phase (narrowphase_igr.hip) and the reverse sweep: one evaluation round over a device-side list
 int launch_igr_list(const DssIgrNet &N, const double *pts, const int *lat_idx, const double *latents, int lat_stride,
                     const int *n_dev, int n_cap, int mode, double *sdf, double *grad, hipStream_t stream, int est)

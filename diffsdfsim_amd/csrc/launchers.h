@@ -16,7 +16,9 @@ int launch_find_contacts_all(const DssWorld &W, int *nc_out, int *body_out, int 
 int launch_find_contacts_box(const DssWorld &W, int *nc_out, int *body_out, int *face_out, double *abc_out,
                              double *geom_out, hipStream_t stream);
 int launch_igr_rounds(const DssWorld &W, hipStream_t stream);
-// igr_mlp.hip: one evaluation round over a device-side point list / over the value list and the gradient list of a query round
+// igr_mlp.hip: the latent size of the network that DssIgrNet.width / .latent name (0, 0 = the 128 / 2 network), -1 = no kernel is
+// built for the shape; one evaluation round over a device-side point list / over the value list and the gradient list of a query round
+int igr_net_latent(const DssIgrNet &N);
 int launch_igr_list(const DssIgrNet &N, const double *pts, const int *lat_idx, const double *latents, int lat_stride,
                     const int *n_dev, int n_cap, int mode, double *sdf, double *grad, hipStream_t stream, int est);
 int launch_igr_pair(const DssIgrNet &N, const double *pts_v, const int *lat_v, const int *n_v, double *sdf_v, const double *pts_g,

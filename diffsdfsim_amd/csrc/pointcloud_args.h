@@ -1,8 +1,6 @@
 // pointcloud_args.h -- what the point-cloud loss launchers (pointcloud_loss.hip, pointcloud_loss_grid_adj.hip) refuse after their
 // null and workspace checks, stated once.  Host code only.
 #pragma once
-#include <vector>
-
 #include "../../include/diffsdfsim_hip.h"
 #include "dss_device.h"
 
@@ -19,17 +17,11 @@ namespace dss {
 inline int pc_judge_segments(int nseg, const int *shape_type, const int *grid_id, int ngrid, const int *grid_dims, hipStream_t st,
                              bool *any_grid = nullptr)
 {
-#if defined(DSS_EMU)
-    const int *types = shape_type, *ids = grid_id, *dims = grid_dims;      // (the emulator's device memory is the host's)
-#else
-    std::vector<int> host_types(nseg), host_ids(grid_id ? nseg : 0), host_dims(3 * (size_t)ngrid);
-    if (hipMemcpyAsync(host_types.data(), shape_type, sizeof(int) * (size_t)nseg, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (grid_id && hipMemcpyAsync(host_ids.data(), grid_id, sizeof(int) * (size_t)nseg, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        (ngrid > 0 && hipMemcpyAsync(host_dims.data(), grid_dims, sizeof(int) * 3 * (size_t)ngrid, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipStreamSynchronize(st) != hipSuccess)
+    HostInts host_types, host_ids, host_dims;
+    if (!host_types.copy(shape_type, nseg, st) || (grid_id && !host_ids.copy(grid_id, nseg, st)) ||
+        (ngrid > 0 && !host_dims.copy(grid_dims, 3 * (size_t)ngrid, st)) || !host_sync(st))
         return DSS_E_BADARG;
-    const int *types = host_types.data(), *ids = grid_id ? host_ids.data() : nullptr, *dims = host_dims.data();
-#endif
+    const int *types = host_types.p, *ids = host_ids.p, *dims = host_dims.p;
     for (int g = 0; g < 3 * ngrid; ++g)
         if (dims[g] < 2) return DSS_E_BADARG;
     bool any = false;

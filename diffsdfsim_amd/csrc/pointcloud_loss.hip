@@ -6,19 +6,16 @@
 //   dss_pointcloud_loss_grids   the same with voxel-grid segments (SHAPE_GRID) from a pooled grid table: a kernel of its own,
 //                         the analytic loops shared
 //
-// One lane per point in a strided loop, 256-thread workgroups, one workgroup per (segment, chunk of a segment) -- a flat
-// grid of nseg * chunks, segment-major; a workgroup covers PC_CHUNK consecutive points of its segment.  Each lane keeps the
-// twelve partial sums in registers; they are combined by a
-// wavefront butterfly (wave_sum) and a fixed tree over the four wavefronts in LDS, and the workgroup writes one partial [12]
-// into the workspace.  A second kernel adds a segment's partials in index order.  No atomics anywhere: the summation
-// order is a function of the launch shape alone, so two calls on the same input return the same bits.
+// One lane per point in a strided loop over the chunk grid of chunk_grid.h (a workgroup per (segment, 2048 consecutive points of
+// it)).  Each lane keeps the twelve partial sums in registers; block_sum writes the workgroup's partial [12] into the workspace and
+// segment_sum_kernel adds a segment's partials in index order.  No atomics anywhere: the summation order is a function of the
+// launch shape alone, so two calls on the same input return the same bits.
 // 24 B read per point against ~1 500 fp64 instructions (the dual-number SDF): VALU-bound, like dss_sdf_query.
 #include "../../include/diffsdfsim_hip.h"
 #include "pointcloud_args.h"
-#include "pointcloud_chunk.h"
+#include "chunk_grid.h"
 #include "../../include/pointcloud_loss.h"
 #include "pointcloud_point.h"
-#include "wave_utils.h"
 
 namespace {
 using namespace dss;
@@ -29,7 +26,7 @@ template <int TYPE> __device__ __forceinline__ void pc_accumulate(const double *
 {
     PcSegment S;
     pc_segment(S, pose, TYPE, prm4);
-    for (int i = i0; i < hi; i += PC_THREADS) {
+    for (int i = i0; i < hi; i += CG_THREADS) {
         const double x[3] = {P[3 * (size_t)i], P[3 * (size_t)i + 1], P[3 * (size_t)i + 2]};
         double term[PC_OUT];
         if (pc_point(S, x, term)) {
@@ -37,20 +34,6 @@ template <int TYPE> __device__ __forceinline__ void pc_accumulate(const double *
             for (int k = 0; k < PC_OUT; ++k) acc[k] += term[k];
         }
     }
-}
-
-// the workgroup's partial [12]: wavefront butterflies, then a fixed tree over the four wavefronts
-__device__ __forceinline__ void pc_reduce(const double *acc, double (*red)[PC_OUT], double *__restrict__ partial)
-{
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < PC_OUT; ++k) {
-        const double w = wave_sum(acc[k]);
-        if (lane_id() == 0) red[tid / WAVE][k] = w;
-    }
-    __syncthreads();
-    if (tid < PC_OUT)
-        partial[(size_t)blockIdx.x * PC_OUT + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
 
 // the segment's shape is the same for the whole workgroup: one loop per primitive, each compiled for its type alone
@@ -68,12 +51,12 @@ __device__ __forceinline__ bool pc_analytic(int type, const double *__restrict__
     return true;
 }
 
-__global__ void __launch_bounds__(PC_THREADS) pointcloud_loss_kernel(int max_seg_len, int chunks, const int *__restrict__ seg_off,
+__global__ void __launch_bounds__(CG_THREADS) pointcloud_loss_kernel(int max_seg_len, int chunks, const int *__restrict__ seg_off,
                                                                     const double *__restrict__ pts, const double *__restrict__ pose,
                                                                     const int *__restrict__ shape_type, const double *__restrict__ prm,
                                                                     double *__restrict__ partial)
 {
-    __shared__ double red[PC_THREADS / WAVE][PC_OUT];
+    __shared__ double red[CG_WAVES][PC_OUT];
     int s, first, lo, hi;
     if (!pc_chunk(max_seg_len, chunks, seg_off, s, first, lo, hi)) return;
     double acc[PC_OUT];
@@ -81,21 +64,21 @@ __global__ void __launch_bounds__(PC_THREADS) pointcloud_loss_kernel(int max_seg
     for (int k = 0; k < PC_OUT; ++k) acc[k] = 0.0;
     if (!pc_analytic(shape_type[s], pts + 3 * (size_t)first, lo + (int)threadIdx.x, hi, pose + 7 * (size_t)s, prm + 4 * (size_t)s, acc))
         return;      // (neural and grid bodies: the launcher has refused them)
-    pc_reduce(acc, red, partial);
+    block_sum<PC_OUT>(acc, red, partial + (size_t)blockIdx.x * PC_OUT);
 }
 
 // The same with voxel-grid segments: type SHAPE_GRID reads the segment's grid from the pooled table.  The value is geom.h's
 // trilinear field and its tangent DiffGridSDF's rule as sdf_unit states it on duals (the once-normalised interpolated
 // central-difference field, not the derivative of the interpolant); the scale is prm[3], a constant, so the three prm
 // tangents stay exactly 0.  The grid pointer and dims go into the segment's Shape, the dual is not widened.
-__global__ void __launch_bounds__(PC_THREADS) pointcloud_loss_grids_kernel(int max_seg_len, int chunks, const int *__restrict__ seg_off,
+__global__ void __launch_bounds__(CG_THREADS) pointcloud_loss_grids_kernel(int max_seg_len, int chunks, const int *__restrict__ seg_off,
                                                                           const double *__restrict__ pts, const double *__restrict__ pose,
                                                                           const int *__restrict__ shape_type, const double *__restrict__ prm,
                                                                           const int *__restrict__ grid_id, const int *__restrict__ grid_off,
                                                                           const int *__restrict__ grid_dims, const double *__restrict__ grid_data,
                                                                           double *__restrict__ partial)
 {
-    __shared__ double red[PC_THREADS / WAVE][PC_OUT];
+    __shared__ double red[CG_WAVES][PC_OUT];
     int s, first, lo, hi;
     if (!pc_chunk(max_seg_len, chunks, seg_off, s, first, lo, hi)) return;
     double acc[PC_OUT];
@@ -109,7 +92,7 @@ __global__ void __launch_bounds__(PC_THREADS) pointcloud_loss_grids_kernel(int m
         pc_segment(S, ps, SHAPE_GRID, pr);
         S.shape.grid = grid_data + grid_off[g];
         for (int i = 0; i < 3; ++i) S.shape.gn[i] = grid_dims[3 * g + i];
-        for (int i = lo + (int)threadIdx.x; i < hi; i += PC_THREADS) {
+        for (int i = lo + (int)threadIdx.x; i < hi; i += CG_THREADS) {
             const double x[3] = {P[3 * (size_t)i], P[3 * (size_t)i + 1], P[3 * (size_t)i + 2]};
             double term[PC_OUT];
             if (pc_point(S, x, term)) {
@@ -120,22 +103,7 @@ __global__ void __launch_bounds__(PC_THREADS) pointcloud_loss_grids_kernel(int m
     } else if (!pc_analytic(type, P, lo + (int)threadIdx.x, hi, ps, pr, acc)) {
         return;      // (neural bodies: the launcher has refused them)
     }
-    pc_reduce(acc, red, partial);
-}
-
-// out[s][k] = the segment's partials added in index order (zero for an empty segment)
-__global__ void __launch_bounds__(PC_THREADS) pointcloud_sum_kernel(int nseg, int max_seg_len, int chunks, const int *__restrict__ seg_off,
-                                                                   const double *__restrict__ partial, double *__restrict__ out)
-{
-    const int t = blockIdx.x * PC_THREADS + threadIdx.x;
-    if (t >= nseg * PC_OUT) return;
-    const int s = t / PC_OUT, k = t - s * PC_OUT;
-    int len = seg_off[s + 1] - seg_off[s];
-    if (len > max_seg_len) len = max_seg_len;
-    const int nch = len > 0 ? (len + PC_CHUNK - 1) / PC_CHUNK : 0;
-    double sum = 0.0;
-    for (int c = 0; c < nch; ++c) sum += partial[((size_t)s * chunks + c) * PC_OUT + k];
-    out[t] = sum;
+    block_sum<PC_OUT>(acc, red, partial + (size_t)blockIdx.x * PC_OUT);
 }
 
 }  // namespace
@@ -160,9 +128,9 @@ int dss_pointcloud_loss(int nseg, int max_seg_len, const int *seg_off, const dou
     if (const int rc = pc_judge_segments(nseg, shape_type, nullptr, 0, nullptr, st)) return rc;
     const int chunks = pc_chunks(max_seg_len);
     if (chunks > 0)
-        hipLaunchKernelGGL(pointcloud_loss_kernel, dim3(chunks * nseg), dim3(PC_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,
+        hipLaunchKernelGGL(pointcloud_loss_kernel, dim3(chunks * nseg), dim3(CG_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,
                            shape_type, prm, (double *)workspace);
-    hipLaunchKernelGGL(pointcloud_sum_kernel, dim3((nseg * PC_OUT + PC_THREADS - 1) / PC_THREADS), dim3(PC_THREADS), 0, st, nseg,
+    hipLaunchKernelGGL(segment_sum_kernel<PC_OUT>, dim3((nseg * PC_OUT + CG_THREADS - 1) / CG_THREADS), dim3(CG_THREADS), 0, st, nseg,
                        max_seg_len, chunks, seg_off, (const double *)workspace, out);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }
@@ -182,9 +150,9 @@ int dss_pointcloud_loss_grids(int nseg, int max_seg_len, const int *seg_off, con
     if (const int rc = pc_judge_segments(nseg, shape_type, grid_id, ngrid, grid_dims, st)) return rc;
     const int chunks = pc_chunks(max_seg_len);
     if (chunks > 0)
-        hipLaunchKernelGGL(pointcloud_loss_grids_kernel, dim3(chunks * nseg), dim3(PC_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,
+        hipLaunchKernelGGL(pointcloud_loss_grids_kernel, dim3(chunks * nseg), dim3(CG_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,
                            shape_type, prm, grid_id, grid_off, grid_dims, grid_data, (double *)workspace);
-    hipLaunchKernelGGL(pointcloud_sum_kernel, dim3((nseg * PC_OUT + PC_THREADS - 1) / PC_THREADS), dim3(PC_THREADS), 0, st, nseg,
+    hipLaunchKernelGGL(segment_sum_kernel<PC_OUT>, dim3((nseg * PC_OUT + CG_THREADS - 1) / CG_THREADS), dim3(CG_THREADS), 0, st, nseg,
                        max_seg_len, chunks, seg_off, (const double *)workspace, out);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }

@@ -7,21 +7,21 @@
 // dss_pointcloud_loss_grids sums -- not DiffGridSDF's rule, which concerns the query point and stays what the pose Jacobian uses.
 // The reference has no such derivative (DiffGridSDF.forward marks the samples non-differentiable).
 //
-// The forward's launch shape (pointcloud_chunk.h): one lane per point, a workgroup per (segment, chunk of 2048 points).  A lane
+// The forward's launch shape (chunk_grid.h): one lane per point, a workgroup per (segment, chunk of 2048 points).  A lane
 // recomputes its point's cell, weights and phi and adds its eight terms with the hardware's fp64 global atomic add
 // (-munsafe-fp-atomics: no compare-and-swap loop), as g_verts in step_bwd_all.hip and the 2-D grid adjoint do.  The order of the
 // adds into one sample is the order of arrival: two calls agree to the rounding of an n-term sum, not in their bits.  Nothing is
 // merged before the adds.
 #include "../../include/diffsdfsim_hip.h"
 #include "pointcloud_args.h"
-#include "pointcloud_chunk.h"
+#include "chunk_grid.h"
 #include "../../include/pointcloud_loss.h"
 #include "pointcloud_point.h"
 
 namespace {
 using namespace dss;
 
-__global__ void __launch_bounds__(PC_THREADS) pointcloud_grid_adjoint_kernel(int max_seg_len, int chunks, const int *__restrict__ seg_off,
+__global__ void __launch_bounds__(CG_THREADS) pointcloud_grid_adjoint_kernel(int max_seg_len, int chunks, const int *__restrict__ seg_off,
                                                                             const double *__restrict__ pts, const double *__restrict__ pose,
                                                                             const int *__restrict__ shape_type, const double *__restrict__ prm,
                                                                             const int *__restrict__ grid_id, const int *__restrict__ grid_off,
@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(PC_THREADS) pointcloud_grid_adjoint_kernel(int
     double *G = g_data + grid_off[g];
     const int n1 = S.shape.gn[1], n2 = S.shape.gn[2];
     const double k0 = 2.0 * gs * val(S.shape.scale);
-    for (int i = lo + (int)threadIdx.x; i < hi; i += PC_THREADS) {
+    for (int i = lo + (int)threadIdx.x; i < hi; i += CG_THREADS) {
         const double x[3] = {P[3 * (size_t)i], P[3 * (size_t)i + 1], P[3 * (size_t)i + 2]};
         int i0[3];
         double w[3], phi;
@@ -74,7 +74,7 @@ extern "C" int dss_pointcloud_loss_grids_adjoint(int nseg, int max_seg_len, cons
     if (const int rc = pc_judge_segments(nseg, shape_type, grid_id, ngrid, grid_dims, st, &any)) return rc;
     const int chunks = pc_chunks(max_seg_len);
     if (!any || chunks == 0) return DSS_OK;      // no grid segment, or no point: nothing to add
-    hipLaunchKernelGGL(pointcloud_grid_adjoint_kernel, dim3(chunks * nseg), dim3(PC_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,
+    hipLaunchKernelGGL(pointcloud_grid_adjoint_kernel, dim3(chunks * nseg), dim3(CG_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,
                        shape_type, prm, grid_id, grid_off, grid_dims, grid_data, g_sum, g_data);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }

@@ -6,22 +6,17 @@
 // observed cloud lies partly outside the estimate's query cube, so the points inside are compacted first and the MFMA kernel of
 // igr_mlp.hip (dss::launch_igr_list, unchanged) walks the compacted list alone:
 //
-//   pci_count_kernel    the chunk grid of pointcloud_loss.hip (256 threads, one workgroup per (segment, 2048 consecutive points),
-//                       segment-major): ballot + popcount of the points inside the cube -> one count per chunk
-//   pci_scan_kernel     one workgroup: exclusive prefix of the chunk counts (wavefront shuffles, the four wavefront totals in LDS,
-//                       a running carry over tiles of 256 chunks) and the total, clamped to the list's capacity, in device memory
-//   pci_emit_kernel     the same walk: a point's slot is its chunk's offset + the points inside before it in index order (the
-//                       (iteration, wavefront) cells before its own from LDS, the lanes below it from the ballot); writes
-//                       u = p / scale, the segment's latent row and the source row
+//   pci_count_kernel    chunk_count over the chunk grid (chunk_grid.h), segment-major: the points inside the cube
+//   chunk_scan_kernel   the chunks' offsets and the total, clamped to the list's capacity, in device memory
+//   pci_emit_kernel     chunk_emit: writes u = p / scale, the segment's latent row and the source row
 //   launch_igr_list     DSS_IGR_XYZ, then DSS_IGR_LATENT (two passes of its own for L = 4).  A device-side length of 0 would be
 //                       safe there (tiles_for gives at least one workgroup and the persistent tile loop `for (base = bid * PTS;
 //                       base < n; ...)` does not run), but the grid and the workgroup shape would be picked for the capacity
 //                       n_pts, not for the list: the host reads the total (one int, the call's only wait, as dss_pointcloud_loss
 //                       reads its shape types) and launches for exactly that length, or not at all for an empty list
 //   pci_reduce_kernel   the chunk grid again: each lane takes its chunk's entries in strided order and forms the 13 terms, the
-//                       pose chain of pointcloud_point.h written out for plain doubles; wavefront butterfly, fixed tree over the
-//                       four wavefronts, one partial [13] per chunk
-//   pci_sum_kernel      out[s][k] = the segment's chunk partials added in index order
+//                       pose chain of pointcloud_point.h written out for plain doubles; block_sum, one partial [13] per chunk
+//   segment_sum_kernel  out[s][k] = the segment's chunk partials added in index order
 //
 // The body-frame point is formed with explicit fused multiply-adds (pci_body_point), so that the three kernels that decide
 // "inside" decide it on the same bits whatever the compiler contracts elsewhere.  No atomics: a segment's row is a function of
@@ -30,12 +25,11 @@
 #include "geom.h"
 #include "launchers.h"
 #include "../../include/pointcloud_loss_igr.h"
-#include "wave_utils.h"
+#include "chunk_grid.h"
 
 namespace {
 using namespace dss;
 
-constexpr int PCI_THREADS = 256, PCI_CHUNK = 2048, PCI_ITERS = PCI_CHUNK / PCI_THREADS, PCI_WAVES = PCI_THREADS / WAVE;
 constexpr int PCI_OUT = DSS_PC_IGR_OUT, PCI_LMAX = DSS_IGR_LATENT_MAX;
 
 struct PciSegment {
@@ -58,20 +52,6 @@ __device__ __forceinline__ bool pci_body_point(const PciSegment &S, const double
     return fabs(p[0]) <= S.scale && fabs(p[1]) <= S.scale && fabs(p[2]) <= S.scale;
 }
 
-// the chunk of workgroup blockIdx.x (pc_chunk of pointcloud_loss.hip): -> false if it holds nothing of its segment
-__device__ __forceinline__ bool pci_chunk(int max_seg_len, int chunks, const int *__restrict__ seg_off, int &s, int &first, int &lo, int &hi)
-{
-    s = blockIdx.x / chunks;
-    const int chunk = blockIdx.x - s * chunks;
-    first = seg_off[s];
-    int len = seg_off[s + 1] - first;
-    if (len > max_seg_len) len = max_seg_len;      // the workspace was sized for max_seg_len
-    lo = chunk * PCI_CHUNK;
-    if (lo >= len) return false;                    // (the whole workgroup)
-    hi = lo + PCI_CHUNK < len ? lo + PCI_CHUNK : len;
-    return true;
-}
-
 // is point i (of the segment's points P, i < hi) inside the segment's cube
 __device__ __forceinline__ bool pci_inside(const PciSegment &S, const double *__restrict__ P, int i, int hi)
 {
@@ -81,95 +61,46 @@ __device__ __forceinline__ bool pci_inside(const PciSegment &S, const double *__
     return pci_body_point(S, x, d, p);
 }
 
-__global__ void __launch_bounds__(PCI_THREADS) pci_count_kernel(int max_seg_len, int chunks, const int *__restrict__ seg_off,
-                                                               const double *__restrict__ pts, const double *__restrict__ pose,
-                                                               const double *__restrict__ scale, int *__restrict__ counts)
+__global__ void __launch_bounds__(CG_THREADS) pci_count_kernel(int max_seg_len, int chunks, const int *__restrict__ seg_off,
+                                                              const double *__restrict__ pts, const double *__restrict__ pose,
+                                                              const double *__restrict__ scale, int *__restrict__ counts)
 {
-    __shared__ int wcount[PCI_WAVES];
     int s, first, lo, hi;
-    if (!pci_chunk(max_seg_len, chunks, seg_off, s, first, lo, hi)) {
+    if (!pc_chunk(max_seg_len, chunks, seg_off, s, first, lo, hi)) {
         if (threadIdx.x == 0) counts[blockIdx.x] = 0;
         return;
     }
     PciSegment S;
     pci_segment(S, pose + 7 * (size_t)s, scale[s]);
     const double *P = pts + 3 * (size_t)first;
-    int n = 0;
-#pragma unroll
-    for (int it = 0; it < PCI_ITERS; ++it) n += __popcll(__ballot(pci_inside(S, P, lo + it * PCI_THREADS + (int)threadIdx.x, hi)));
-    if (lane_id() == 0) wcount[threadIdx.x / WAVE] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = (wcount[0] + wcount[1]) + (wcount[2] + wcount[3]);
+    const int n = chunk_count(lo, [&](int i) { return pci_inside(S, P, i, hi); });
+    if (threadIdx.x == 0) counts[blockIdx.x] = n;
 }
 
-__global__ void __launch_bounds__(PCI_THREADS) pci_scan_kernel(int nwg, int cap, const int *__restrict__ counts, int *__restrict__ offs,
-                                                              int *__restrict__ total)
+__global__ void __launch_bounds__(CG_THREADS) pci_emit_kernel(int max_seg_len, int chunks, int cap, const int *__restrict__ seg_off,
+                                                             const double *__restrict__ pts, const double *__restrict__ pose,
+                                                             const double *__restrict__ scale, const int *__restrict__ lat_idx,
+                                                             const int *__restrict__ offs, double *__restrict__ qpts,
+                                                             int *__restrict__ qlat, int *__restrict__ qsrc)
 {
-    __shared__ int wsum[PCI_WAVES];
-    const int tid = threadIdx.x, lane = lane_id(), wv = tid / WAVE;
-    int carry = 0;
-    for (int base = 0; base < nwg; base += PCI_THREADS) {
-        const int i = base + tid, c = i < nwg ? counts[i] : 0;
-        int inc = c;
-#pragma unroll
-        for (int o = 1; o < WAVE; o <<= 1) {
-            const int v = __shfl_up(inc, o, WAVE);
-            if (lane >= o) inc += v;
-        }
-        if (lane == WAVE - 1) wsum[wv] = inc;
-        __syncthreads();
-        int before = 0;
-        for (int w = 0; w < wv; ++w) before += wsum[w];
-        if (i < nwg) offs[i] = carry + before + inc - c;
-        carry += (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-        __syncthreads();      // the next tile overwrites wsum
-    }
-    if (tid == 0) total[0] = carry < cap ? carry : cap;
-}
-
-__global__ void __launch_bounds__(PCI_THREADS) pci_emit_kernel(int max_seg_len, int chunks, int cap, const int *__restrict__ seg_off,
-                                                              const double *__restrict__ pts, const double *__restrict__ pose,
-                                                              const double *__restrict__ scale, const int *__restrict__ lat_idx,
-                                                              const int *__restrict__ offs, double *__restrict__ qpts,
-                                                              int *__restrict__ qlat, int *__restrict__ qsrc)
-{
-    __shared__ int cell[PCI_ITERS][PCI_WAVES];
     int s, first, lo, hi;
-    if (!pci_chunk(max_seg_len, chunks, seg_off, s, first, lo, hi)) return;
+    if (!pc_chunk(max_seg_len, chunks, seg_off, s, first, lo, hi)) return;
     PciSegment S;
     pci_segment(S, pose + 7 * (size_t)s, scale[s]);
     const double *P = pts + 3 * (size_t)first;
-    const int tid = threadIdx.x, lane = lane_id(), wv = tid / WAVE;
-    unsigned long long mask[PCI_ITERS];
-#pragma unroll
-    for (int it = 0; it < PCI_ITERS; ++it) {
-        mask[it] = __ballot(pci_inside(S, P, lo + it * PCI_THREADS + tid, hi));
-        if (lane == 0) cell[it][wv] = __popcll(mask[it]);
-    }
-    __syncthreads();
     const int row = lat_idx[s];
-    int at = offs[blockIdx.x];
-#pragma unroll
-    for (int it = 0; it < PCI_ITERS; ++it) {
-        int mine = at;
-        for (int w = 0; w < wv; ++w) mine += cell[it][w];
-        if ((mask[it] >> lane) & 1ull) {
-            const int slot = mine + __popcll(mask[it] & ((1ull << lane) - 1ull)), i = lo + it * PCI_THREADS + tid;
-            if (slot < cap) {
-                const double x[3] = {P[3 * (size_t)i], P[3 * (size_t)i + 1], P[3 * (size_t)i + 2]};
-                double d[3], p[3];
-                pci_body_point(S, x, d, p);
-                for (int k = 0; k < 3; ++k) qpts[3 * (size_t)slot + k] = p[k] / S.scale;      // (a division, as query_sdfs writes it)
-                qlat[slot] = row;
-                qsrc[slot] = first + i;
-            }
-        }
-        at += (cell[it][0] + cell[it][1]) + (cell[it][2] + cell[it][3]);
-    }
+    chunk_emit(lo, [&](int i) { return pci_inside(S, P, i, hi); }, offs, cap, [&](int slot, int i) {
+        const double x[3] = {P[3 * (size_t)i], P[3 * (size_t)i + 1], P[3 * (size_t)i + 2]};
+        double d[3], p[3];
+        pci_body_point(S, x, d, p);
+        for (int k = 0; k < 3; ++k) qpts[3 * (size_t)slot + k] = p[k] / S.scale;      // (a division, as query_sdfs writes it)
+        qlat[slot] = row;
+        qsrc[slot] = first + i;
+    });
 }
 
 // GS: doubles per row of glat (launch_igr_list's DSS_IGR_LATENT: 3 for L <= 3, L beyond); L: the network's latent size
-__global__ void __launch_bounds__(PCI_THREADS) pci_reduce_kernel(int max_seg_len, int chunks, int cap, int L, int GS,
+__global__ void __launch_bounds__(CG_THREADS) pci_reduce_kernel(int max_seg_len, int chunks, int cap, int L, int GS,
                                                                 const int *__restrict__ seg_off, const double *__restrict__ pts,
                                                                 const double *__restrict__ pose, const double *__restrict__ scale,
                                                                 const int *__restrict__ counts, const int *__restrict__ offs,
@@ -177,9 +108,9 @@ __global__ void __launch_bounds__(PCI_THREADS) pci_reduce_kernel(int max_seg_len
                                                                 const double *__restrict__ gxyz, const double *__restrict__ glat,
                                                                 double *__restrict__ partial)
 {
-    __shared__ double red[PCI_WAVES][PCI_OUT];
+    __shared__ double red[CG_WAVES][PCI_OUT];
     int s, first, lo, hi;
-    if (!pci_chunk(max_seg_len, chunks, seg_off, s, first, lo, hi)) return;
+    if (!pc_chunk(max_seg_len, chunks, seg_off, s, first, lo, hi)) return;
     PciSegment S;
     pci_segment(S, pose + 7 * (size_t)s, scale[s]);
     const double two_s = 2.0 / (S.q[0] * S.q[0] + S.q[1] * S.q[1] + S.q[2] * S.q[2] + S.q[3] * S.q[3]);
@@ -192,7 +123,7 @@ __global__ void __launch_bounds__(PCI_THREADS) pci_reduce_kernel(int max_seg_len
     double acc[PCI_OUT];
 #pragma unroll
     for (int k = 0; k < PCI_OUT; ++k) acc[k] = 0.0;
-    for (int e = e0 + tid; e < e1; e += PCI_THREADS) {
+    for (int e = e0 + tid; e < e1; e += CG_THREADS) {
         // the quaternion chain needs d = x - pos beside p, and u = p / scale does not give it back exactly: the entry names its
         // source row and the point is formed again, on the bits the mask was decided on
         const size_t src = (size_t)qsrc[e];
@@ -223,37 +154,7 @@ __global__ void __launch_bounds__(PCI_THREADS) pci_reduce_kernel(int max_seg_len
         for (int k = 0; k < PCI_LMAX; ++k)
             if (k < L) acc[9 + k] += kz * glat[(size_t)GS * e + k];
     }
-#pragma unroll
-    for (int k = 0; k < PCI_OUT; ++k) {
-        const double w = wave_sum(acc[k]);
-        if (lane_id() == 0) red[tid / WAVE][k] = w;
-    }
-    __syncthreads();
-    if (tid < PCI_OUT) partial[(size_t)blockIdx.x * PCI_OUT + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-}
-
-// out[s][k] = the segment's partials added in index order (zero for an empty segment)
-__global__ void __launch_bounds__(PCI_THREADS) pci_sum_kernel(int nseg, int max_seg_len, int chunks, const int *__restrict__ seg_off,
-                                                             const double *__restrict__ partial, double *__restrict__ out)
-{
-    const int t = blockIdx.x * PCI_THREADS + threadIdx.x;
-    if (t >= nseg * PCI_OUT) return;
-    const int s = t / PCI_OUT, k = t - s * PCI_OUT;
-    int len = seg_off[s + 1] - seg_off[s];
-    if (len > max_seg_len) len = max_seg_len;
-    const int nch = len > 0 ? (len + PCI_CHUNK - 1) / PCI_CHUNK : 0;
-    double sum = 0.0;
-    for (int c = 0; c < nch; ++c) sum += partial[((size_t)s * chunks + c) * PCI_OUT + k];
-    out[t] = sum;
-}
-
-int pci_chunks(int max_seg_len) { return (max_seg_len + PCI_CHUNK - 1) / PCI_CHUNK; }
-
-// the network's latent size, as igr_mlp.hip reads DssIgrNet (0, 0 = the 128 / 2 network); -1 = no kernel is built for the shape
-int pci_latent(const DssIgrNet &N)
-{
-    const int w = N.width ? N.width : 128, l = N.latent ? N.latent : 2;
-    return ((w == 128 && l == 2) || (w == 256 && l == 4)) ? l : -1;
+    block_sum<PCI_OUT>(acc, red, partial + (size_t)blockIdx.x * PCI_OUT);
 }
 
 // the workspace: doubles first, then ints
@@ -265,7 +166,7 @@ struct PciWorkspace {
 // base == NULL: only .bytes is set
 PciWorkspace pci_layout(void *base, int nseg, int max_seg_len, int n_pts)
 {
-    const size_t nwg = (size_t)nseg * pci_chunks(max_seg_len), n = (size_t)n_pts;
+    const size_t nwg = (size_t)nseg * pc_chunks(max_seg_len), n = (size_t)n_pts;
     const size_t nd = nwg * PCI_OUT + (3 + 1 + 3 + PCI_LMAX) * n, ni = 2 * nwg + 2 + 2 * n;
     PciWorkspace W = {};
     W.bytes = nd * sizeof(double) + ((ni * sizeof(int) + 7) & ~(size_t)7);
@@ -302,42 +203,38 @@ int dss_pointcloud_loss_igr(const DssIgrNet *net, int nseg, int max_seg_len, con
     if (!net || !net->W0 || !net->b0 || !net->Wp || !net->bh || !net->W8 || !net->b8) return DSS_E_BADARG;
     if (nseg <= 0 || max_seg_len < 0 || n_pts < 0 || !seg_off || !pose || !scale || !lat_idx || !latents || !out) return DSS_E_BADARG;
     if (max_seg_len > 0 && n_pts > 0 && !pts) return DSS_E_BADARG;
-    const int L = pci_latent(*net);
+    const int L = igr_net_latent(*net);
     if (L < 0) return DSS_E_UNSUPPORTED;
     if (lat_stride < L) return DSS_E_BADARG;
     if (n_pts == 0) max_seg_len = 0;      // (no row of pts may be named: every segment is empty)
-    if ((long long)nseg * (pci_chunks(max_seg_len) > 0 ? pci_chunks(max_seg_len) : 1) > 0x7fffffffLL / PCI_OUT || n_pts > 0x7fffffff / 12)
+    if ((long long)nseg * (pc_chunks(max_seg_len) > 0 ? pc_chunks(max_seg_len) : 1) > 0x7fffffffLL / PCI_OUT || n_pts > 0x7fffffff / 12)
         return DSS_E_UNSUPPORTED;      // grid.x and the int indices nseg * chunks * 13, 3 n_pts, 4 n_pts
     const size_t need = dss_pointcloud_loss_igr_workspace_bytes(nseg, max_seg_len, n_pts);
     if (need > 0 && (!workspace || workspace_bytes < need)) return DSS_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int chunks = pci_chunks(max_seg_len), nwg = chunks * nseg;
+    const int chunks = pc_chunks(max_seg_len), nwg = chunks * nseg;
     const PciWorkspace W = pci_layout(workspace, nseg, max_seg_len, n_pts);
     if (chunks > 0) {
-        hipLaunchKernelGGL(pci_count_kernel, dim3(nwg), dim3(PCI_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose, scale, W.counts);
-        hipLaunchKernelGGL(pci_scan_kernel, dim3(1), dim3(PCI_THREADS), 0, st, nwg, n_pts, (const int *)W.counts, W.offs, W.total);
-        hipLaunchKernelGGL(pci_emit_kernel, dim3(nwg), dim3(PCI_THREADS), 0, st, max_seg_len, chunks, n_pts, seg_off, pts, pose, scale, lat_idx,
+        hipLaunchKernelGGL(pci_count_kernel, dim3(nwg), dim3(CG_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose, scale, W.counts);
+        hipLaunchKernelGGL(chunk_scan_kernel<>, dim3(1), dim3(CG_THREADS), 0, st, nwg, n_pts, (const int *)W.counts, W.offs, W.total);
+        hipLaunchKernelGGL(pci_emit_kernel, dim3(nwg), dim3(CG_THREADS), 0, st, max_seg_len, chunks, n_pts, seg_off, pts, pose, scale, lat_idx,
                            (const int *)W.offs, W.qpts, W.qlat, W.qsrc);
         // The list's length decides the network's grid and workgroup shape, and it is usually far below n_pts (the part of the
         // clouds inside the cubes): the host reads it -- one int, the call's only wait -- and launches for exactly that many points.
-        int total = 0;
-#if defined(DSS_EMU)
-        total = W.total[0];      // (the emulator's device memory is the host's)
-#else
-        if (hipMemcpyAsync(&total, W.total, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return DSS_E_BADARG;      // (the runtime refused a pointer: as dss_pointcloud_loss reports its read)
-#endif
+        HostInts host_total;
+        if (!host_total.copy(W.total, 1, st) || !host_sync(st)) return DSS_E_BADARG;      // (as dss_pointcloud_loss reports its read)
+        const int total = host_total.p[0];
         if (total > 0) {
             int rc = dss::launch_igr_list(*net, W.qpts, W.qlat, latents, lat_stride, nullptr, total, DSS_IGR_XYZ, W.sdf, W.gxyz, st, -1);
             if (rc == DSS_OK)
                 rc = dss::launch_igr_list(*net, W.qpts, W.qlat, latents, lat_stride, nullptr, total, DSS_IGR_LATENT, W.sdf, W.glat, st, -1);      // (writes the same values again)
             if (rc != DSS_OK) return rc;
         }
-        hipLaunchKernelGGL(pci_reduce_kernel, dim3(nwg), dim3(PCI_THREADS), 0, st, max_seg_len, chunks, n_pts, L, L > 3 ? L : 3, seg_off, pts,
+        hipLaunchKernelGGL(pci_reduce_kernel, dim3(nwg), dim3(CG_THREADS), 0, st, max_seg_len, chunks, n_pts, L, L > 3 ? L : 3, seg_off, pts,
                            pose, scale, (const int *)W.counts, (const int *)W.offs, (const int *)W.qsrc, (const double *)W.sdf,
                            (const double *)W.gxyz, (const double *)W.glat, W.partial);
     }
-    hipLaunchKernelGGL(pci_sum_kernel, dim3((nseg * PCI_OUT + PCI_THREADS - 1) / PCI_THREADS), dim3(PCI_THREADS), 0, st, nseg, max_seg_len,
+    hipLaunchKernelGGL(segment_sum_kernel<PCI_OUT>, dim3((nseg * PCI_OUT + CG_THREADS - 1) / CG_THREADS), dim3(CG_THREADS), 0, st, nseg, max_seg_len,
                        chunks, seg_off, (const double *)W.partial, out);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }

@@ -11,7 +11,6 @@
 //
 // fp64 VALU throughout; no atomics, so every output is a function of the input alone.
 #include <math.h>
-#include <vector>
 
 #include "depth_trace.h"
 #include "../../include/shade_camera.h"
@@ -200,17 +199,11 @@ extern "C" int dss_shade_render(int nview, int nbody, const double *pose, const 
     // shape types, grid ids and the grids' dims decide the status, so the host reads them before anything is enqueued
     hipStream_t st = (hipStream_t)stream;
     const size_t ntype = (size_t)nview * nbody;
-#if defined(DSS_EMU)
-    const int *types = shape_type, *ids = ngrid > 0 ? grid_id : nullptr, *dims = grid_dims;      // (the emulator's device memory is the host's)
-#else
-    std::vector<int> host_types(ntype), host_ids(ntype), host_dims(3 * (size_t)ngrid);
-    if (hipMemcpyAsync(host_types.data(), shape_type, sizeof(int) * ntype, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (ngrid > 0 && (hipMemcpyAsync(host_ids.data(), grid_id, sizeof(int) * ntype, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                       hipMemcpyAsync(host_dims.data(), grid_dims, sizeof(int) * 3 * (size_t)ngrid, hipMemcpyDeviceToHost, st) != hipSuccess)) ||
-        hipStreamSynchronize(st) != hipSuccess)
+    HostInts host_types, host_ids, host_dims;
+    if (!host_types.copy(shape_type, ntype, st) ||
+        (ngrid > 0 && (!host_ids.copy(grid_id, ntype, st) || !host_dims.copy(grid_dims, 3 * (size_t)ngrid, st))) || !host_sync(st))
         return DSS_E_BADARG;
-    const int *types = host_types.data(), *ids = ngrid > 0 ? host_ids.data() : nullptr, *dims = host_dims.data();
-#endif
+    const int *types = host_types.p, *ids = host_ids.p, *dims = host_dims.p;
     for (int g = 0; g < 3 * ngrid; ++g)
         if (dims[g] < 2) return DSS_E_BADARG;
     bool any = false;

@@ -152,6 +152,13 @@ def named(k, names):
     return [index_of(k, n) for n in names]
 
 
+def many_segments(n=257):
+    """n golden segments (network 0) of a handful of points each (an empty one among them), cycled: one chunk per segment, so the
+    call has n workgroups and the scan of their counts carries over a tile of 256."""
+    pick = named(0, ["one_point", "fd_nonunit_6", "empty", "pair_a", "nonunit_25"])
+    return [pick[i % len(pick)] for i in range(n)]
+
+
 def central_difference_segments(k, name="mixed_257", h=1e-6):
     """2 (7 + L) copies of one golden segment, each with one pose component or one latent coordinate moved by +-h: one call gives
     every value the central differences need.  -> ids, pose [n][7], latent table, lat_rows."""

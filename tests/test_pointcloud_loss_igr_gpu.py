@@ -65,6 +65,15 @@ def test_only_empty_segments_need_no_workspace_and_give_zeros(backend, packed):
     assert c.nbytes == 0 and c.run() == 0 and np.all(c.result() == 0.0)
 
 
+def test_257_workgroups_carry_the_scan_over_a_tile(backend, packed, full):
+    ids = C.many_segments()
+    out = C.launch(backend, packed[0], 0, ids)
+    C.check_against_golden(out[:5], ids[:5], "gpu 257")
+    C.check_exact_zeros(out, ids, 0)
+    for row, s in zip(out, ids):      # a segment's row does not depend on where the list puts its points
+        assert np.array_equal(row, full[0][C.segments_of(0).index(s)]), C.golden()["names"][s]
+
+
 @pytest.mark.parametrize("k", [0, 1])
 def test_central_differences_in_pose_and_latent(backend, packed, full, k):
     ids, pose, table, rows = C.central_difference_segments(k)
@@ -77,16 +86,14 @@ def test_return_codes(backend, packed, k):
     C.check_return_codes(backend, packed[k], k)
 
 
-@pytest.mark.parametrize("k", [0, 1])
-def test_dense_4133_points_all_inside_against_igr_query_and_torch(backend, packed, k):
-    """Three chunks, every point inside: the terms from igr.igr_query (the same network kernel on the uncompacted points) and
-    torch double arithmetic on the device.  d_ref = the distance between torch's sum over the points in index order (cumsum) and
-    its own tree (sum): the bound is max(16 d_ref, 1e-12 abs_sum) as for the golden."""
+def built_segment(backend, packed, k, r, pb, scale):
+    """One segment built here from body-frame points pb (each 1e-6 scale or more from the cube's faces; a random pose from r): the
+    terms of the points inside from igr.igr_query (the same network kernel on the uncompacted points) and torch double arithmetic
+    on the device.  d_ref = the distance between torch's sum over the points in index order (cumsum) and its own tree (sum): the
+    bound is max(16 d_ref, 1e-12 abs_sum) as for the golden.  -> out [13], tree, bound, inside [n] (bool), the workspace's ints."""
     from diffsdfsim_amd import igr
     g, L = C.golden(), C.latent_size(k)
     dev = backend.device
-    r = np.random.default_rng(5 + k)
-    n, scale = 4096 + 37, 0.9
     q = r.standard_normal(4); q *= 1.1 / np.linalg.norm(q)
     pos = r.uniform(-1, 1, 3)
     z = g["latents_%d" % k][1]
@@ -97,11 +104,13 @@ def test_dense_4133_points_all_inside_against_igr_query_and_torch(backend, packe
     N = torch.stack([torch.stack([-(j * j + kk * kk), i * j - kk * rr, i * kk + j * rr]), torch.stack([i * j + kk * rr, -(i * i + kk * kk), j * kk - i * rr]),
                      torch.stack([i * kk - j * rr, j * kk + i * rr, -(i * i + j * j)])])
     R = torch.eye(3, dtype=torch.float64, device=dev) + s2 * N
-    pb = t(r.uniform(-0.97 * scale, 0.97 * scale, (n, 3)))
-    x = (pb @ R.T + post).contiguous()
-    d = x - post
-    p = d @ R
-    assert bool((p.abs() < scale * (1 - 1e-6)).all())
+    x = (t(pb(r) if callable(pb) else pb) @ R.T + post).contiguous()
+    n = len(x)
+    d_all = x - post
+    p_all = d_all @ R
+    inside = (p_all.abs() < scale * (1 - 1e-6)).all(1)
+    assert bool((inside | (p_all.abs() > scale * (1 + 1e-6)).any(1)).all())      # nobody near a face
+    d, p = d_all[inside], p_all[inside]
     u = (p / scale).contiguous()
     phi, gu = igr.igr_query(u, t(z), packed[k])
     _phi, gz = igr.igr_query(u, t(z), packed[k], wrt="latent")
@@ -111,7 +120,7 @@ def test_dense_4133_points_all_inside_against_igr_query_and_torch(backend, packe
           torch.stack([torch.stack([zero, j, kk]), torch.stack([j, -2 * i, -rr]), torch.stack([kk, rr, -2 * i])]),
           torch.stack([torch.stack([-2 * j, i, rr]), torch.stack([i, zero, kk]), torch.stack([-rr, kk, -2 * j])]),
           torch.stack([torch.stack([-2 * kk, -rr, i]), torch.stack([rr, -2 * kk, j]), torch.stack([i, j, zero])])]
-    T = torch.zeros(n, C.OUT, dtype=torch.float64, device=dev)
+    T = torch.zeros(len(u), C.OUT, dtype=torch.float64, device=dev)
     T[:, 0] = (scale * phi) ** 2
     T[:, 1] = 1
     for m in range(4):
@@ -129,7 +138,47 @@ def test_dense_4133_points_all_inside_against_igr_query_and_torch(backend, packe
     arrs = [up(np.array([0, n], np.int32)), x, up(np.concatenate([q, pos])[None]), up(np.array([scale])), up(np.array([1], np.int32)), up(table)]
     rc = C.raw_call(backend, H.net_struct(backend, packed[k]), 1, n, *arrs, C.LAT_STRIDE, n, out, ws, nbytes)
     assert rc == 0
-    got = backend.to_numpy(out)[0]
+    nwg = (n + 2047) // 2048      # the workspace (pointcloud_loss_igr.hip: pci_layout): doubles, then counts, offs, total[2], qlat, qsrc
+    ints = ws[nwg * C.OUT + 11 * n:].view(torch.int32).cpu().numpy()
+    return backend.to_numpy(out)[0], tree, bound, inside.cpu().numpy(), ints
+
+
+@pytest.mark.parametrize("k", [0, 1])
+def test_dense_4133_points_all_inside_against_igr_query_and_torch(backend, packed, k):
+    """Three chunks, every point inside."""
+    r = np.random.default_rng(5 + k)
+    n, scale = 4096 + 37, 0.9
+    got, tree, bound, inside, _ints = built_segment(backend, packed, k, r, lambda r: r.uniform(-0.97 * scale, 0.97 * scale, (n, 3)), scale)
     err = np.abs(got - tree)
     print("MI355X net %d dense_4133 measured / bound %.3f" % (k, float(np.max(np.where(bound > 0, err / np.where(bound > 0, bound, 1), 0.0)))))
-    assert got[1] == n and np.all(err <= bound), (got, tree, bound)
+    assert inside.all() and got[1] == n and np.all(err <= bound), (got, tree, bound)
+
+
+def seam_points(shape, r, scale):
+    """2049: every point inside (a full chunk of all-ones ballots, then a chunk whose only live lane is thread 0 of its first
+    iteration); 64_64: 64 points inside, then 64 outside (an all-ones and an all-zero ballot, lane 63 the last one in)."""
+    n, n_in = (2049, 2049) if shape == "2049" else (128, 64)
+    pb = r.uniform(-0.97 * scale, 0.97 * scale, (n, 3))
+    axis = r.integers(0, 3, n - n_in)
+    pb[np.arange(n_in, n), axis] = r.choice([-1.0, 1.0], n - n_in) * r.uniform(1.03 * scale, 1.5 * scale, n - n_in)
+    return pb
+
+
+@pytest.mark.parametrize("shape", ["2049", "64_64"])
+@pytest.mark.parametrize("k", [0, 1])
+def test_full_and_empty_ballots_and_a_chunk_of_one_point(backend, packed, k, shape):
+    """The compaction's edges on a segment built here: counts, offsets, total and the order of the emitted source rows are exact,
+    the sums within built_segment's bound."""
+    r = np.random.default_rng(11 + k)
+    scale = 0.9
+    pb = seam_points(shape, r, scale)
+    got, tree, bound, inside, ints = built_segment(backend, packed, k, r, pb, scale)
+    n, nwg = len(pb), (len(pb) + 2047) // 2048
+    want = np.array([64] if shape == "64_64" else [2048, 1])
+    assert np.array_equal(inside, np.arange(n) < want.sum())
+    counts, offs, total, qsrc = ints[:nwg], ints[nwg:2 * nwg], ints[2 * nwg], ints[2 * nwg + 2 + n:2 * nwg + 2 + 2 * n]
+    assert np.array_equal(counts, want) and np.array_equal(offs, np.cumsum(want) - want) and total == want.sum()
+    assert np.array_equal(qsrc[:total], np.nonzero(inside)[0])
+    err = np.abs(got - tree)
+    print("MI355X net %d %s measured / bound %.3f" % (k, shape, float(np.max(np.where(bound > 0, err / np.where(bound > 0, bound, 1), 0.0)))))
+    assert got[1] == want.sum() and np.all(err <= bound), (got, tree, bound)
