@@ -17,6 +17,7 @@
 // Grid samples: a lane adds its eight terms with the hardware's fp64 global atomic add (-munsafe-fp-atomics), as
 // pointcloud_loss_grid_adj.hip does; the order of the adds into one sample is the order of arrival.
 #include "depth_trace.h"
+#include "shape_args.h"
 #include "depth_adjoint.h"
 #include "depth_adjoint_point.h"
 
@@ -166,20 +167,15 @@ __global__ void __launch_bounds__(WAVE) depth_adjoint_sum_kernel(int nbody, int 
     }
 }
 
-inline int da_tiles(int W, int H) { return ((W + DC_TILE - 1) / DC_TILE) * ((H + DC_TILE - 1) / DC_TILE); }
-inline bool da_shape_ok(int nview, int nbody, int W, int H)
-{
-    return nbody <= DC_MAX_BODY && dc_images_ok(nview, H, W) && (long long)da_tiles(W, H) * nview <= 0x7fffffffLL;      // grid.x
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t dss_depth_adjoint_workspace_bytes(int nview, int nbody, int W, int H)
 {
-    if (nview <= 0 || nbody <= 0 || W <= 0 || H <= 0 || !da_shape_ok(nview, nbody, W, H)) return 0;
-    return (size_t)nview * da_tiles(W, H) * nbody * DA_TERMS * sizeof(double);
+    const DcLaunch L = dc_launch_shape(nview, nbody, W, H);
+    if (nbody <= 0 || !L.ok) return 0;
+    return (size_t)nview * L.tiles_per_view * nbody * DA_TERMS * sizeof(double);
 }
 
 int dss_depth_adjoint(int nview, int nbody, const double *pose, const int *shape_type, const double *prm, const double *cam, double fx,
@@ -192,32 +188,18 @@ int dss_depth_adjoint(int nview, int nbody, const double *pose, const int *shape
         return DSS_E_BADARG;
     if (ngrid > 0 && (!grid_id || !grid_off || !grid_dims || !grid_data)) return DSS_E_BADARG;
     if (!(fx != 0.0) || !(fy != 0.0) || !(min_cos >= 0.0) || !(min_cos <= 1.0)) return DSS_E_BADARG;
-    if (!da_shape_ok(nview, nbody, W, H)) return DSS_E_UNSUPPORTED;
+    const DcLaunch L = dc_launch_shape(nview, nbody, W, H);
+    if (!L.ok) return DSS_E_UNSUPPORTED;
     const size_t need = dss_depth_adjoint_workspace_bytes(nview, nbody, W, H);
     if (!workspace || workspace_bytes < need) return DSS_E_WORKSPACE;
-    // shape types, grid ids and the grids' dims decide the status, as in dss_depth_render_grids: the host reads them first
+    // Shape types, grid ids and the grids' dims decide the status, as in dss_shade_render: the host reads them first; without a
+    // table (ngrid = 0) grid_id is not read, and a level-set body has no grid.
     hipStream_t st = (hipStream_t)stream;
-    const size_t ntype = (size_t)nview * nbody;
-    const bool table = grid_id != nullptr && ngrid > 0;
-    HostInts host_types, host_ids, host_dims;
-    if (!host_types.copy(shape_type, ntype, st) || (table && !host_ids.copy(grid_id, ntype, st)) ||
-        (table && !host_dims.copy(grid_dims, 3 * (size_t)ngrid, st)) || !host_sync(st))
-        return DSS_E_BADARG;
-    const int *types = host_types.p, *ids = host_ids.p, *dims = host_dims.p;
-    if (table)
-        for (int g = 0; g < 3 * ngrid; ++g)
-            if (dims[g] < 2) return DSS_E_BADARG;
     bool any = false;
-    for (size_t i = 0; i < ntype; ++i) {
-        const bool level_set = types[i] == DSS_SHAPE_GRID || types[i] == DSS_SHAPE_IGR;
-        if (level_set && ids && ids[i] >= ngrid) return DSS_E_BADARG;
-        if (level_set && (!ids || ids[i] < 0)) return DSS_E_UNSUPPORTED;      // a grid or neural body without a grid
-        if (!level_set && types[i] != DSS_SHAPE_BOX && types[i] != DSS_SHAPE_SPHERE && types[i] != DSS_SHAPE_CYLINDER &&
-            types[i] != DSS_SHAPE_BOX_ROUNDED)
-            return DSS_E_UNSUPPORTED;      // brick, bowl: as in dss_depth_render
-        if (level_set) any = true;
-    }
-    const int tiles_x = (W + DC_TILE - 1) / DC_TILE, tiles_per_view = da_tiles(W, H);
+    if (const int rc = judge_shapes((size_t)nview * nbody, shape_type, SHAPES_CONVEX, SHAPES_GRID_IGR, ngrid > 0 ? grid_id : nullptr, ngrid,
+                                    grid_dims, st, &any))
+        return rc;
+    const int tiles_x = L.tiles_x, tiles_per_view = L.tiles_per_view;
     double *partial = (double *)workspace;
     if (any)
         hipLaunchKernelGGL(depth_adjoint_kernel<true>, dim3(tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, tiles_x, tiles_per_view,

@@ -18,6 +18,7 @@
 // The tables, the ray, the slab test and the traces are those of depth_trace.h, which the colour camera shares.
 #include "chunk_grid.h"
 #include "depth_trace.h"
+#include "shape_args.h"
 
 namespace {
 
@@ -154,19 +155,13 @@ int dss_depth_render(int nview, int nbody, const double *pose, const int *shape_
 {
     if (nview <= 0 || nbody <= 0 || W <= 0 || H <= 0 || !pose || !shape_type || !prm || !cam || !depth || !seg) return DSS_E_BADARG;
     if (!(fx != 0.0) || !(fy != 0.0) || !(znear >= 0.0) || !(znear < zfar)) return DSS_E_BADARG;
-    if (nbody > DC_MAX_BODY || !dc_images_ok(nview, H, W)) return DSS_E_UNSUPPORTED;
-    const int tiles_x = (W + DC_TILE - 1) / DC_TILE, tiles_per_view = tiles_x * ((H + DC_TILE - 1) / DC_TILE);
-    if ((long long)tiles_per_view * nview > 0x7fffffffLL) return DSS_E_UNSUPPORTED;      // grid.x
-    // the shape types decide the status, so the host reads them before anything is enqueued
+    const DcLaunch L = dc_launch_shape(nview, nbody, W, H);
+    if (!L.ok) return DSS_E_UNSUPPORTED;
+    // The shape types decide the status, so the host reads them before anything is enqueued.  Brick, bowl: not shown to bound the
+    // distance; neural and grid bodies: not in this renderer (no table: a level-set body has no grid).
     hipStream_t st = (hipStream_t)stream;
-    const size_t ntype = (size_t)nview * nbody;
-    HostInts host_types;
-    if (!host_types.copy(shape_type, ntype, st) || !host_sync(st)) return DSS_E_BADARG;
-    const int *types = host_types.p;
-    for (size_t i = 0; i < ntype; ++i)
-        if (types[i] != DSS_SHAPE_BOX && types[i] != DSS_SHAPE_SPHERE && types[i] != DSS_SHAPE_CYLINDER && types[i] != DSS_SHAPE_BOX_ROUNDED)
-            return DSS_E_UNSUPPORTED;      // brick, bowl: not shown to bound the distance; neural and grid bodies: not in this renderer
-    hipLaunchKernelGGL(depth_render_kernel, dim3(tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, tiles_x, tiles_per_view, pose,
+    if (const int rc = judge_shapes((size_t)nview * nbody, shape_type, SHAPES_CONVEX, SHAPES_GRID_IGR, nullptr, 0, nullptr, st)) return rc;
+    hipLaunchKernelGGL(depth_render_kernel, dim3(L.tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, L.tiles_x, L.tiles_per_view, pose,
                        shape_type, prm, cam, fx, fy, cx, cy, W, H, znear, zfar, depth, seg);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }
@@ -189,36 +184,20 @@ int dss_depth_render_grids(int nview, int nbody, const double *pose, const int *
         return DSS_E_BADARG;
     if (ngrid > 0 && (!grid_off || !grid_dims || !grid_data || !blk_off || !blk_min)) return DSS_E_BADARG;
     if (!(fx != 0.0) || !(fy != 0.0) || !(znear >= 0.0) || !(znear < zfar)) return DSS_E_BADARG;
-    if (nbody > DC_MAX_BODY || !dc_images_ok(nview, H, W)) return DSS_E_UNSUPPORTED;
-    const int tiles_x = (W + DC_TILE - 1) / DC_TILE, tiles_per_view = tiles_x * ((H + DC_TILE - 1) / DC_TILE);
-    if ((long long)tiles_per_view * nview > 0x7fffffffLL) return DSS_E_UNSUPPORTED;      // grid.x
+    const DcLaunch L = dc_launch_shape(nview, nbody, W, H);
+    if (!L.ok) return DSS_E_UNSUPPORTED;
     // shape types, grid ids and the grids' dims decide the status, so the host reads them before anything is enqueued
     hipStream_t st = (hipStream_t)stream;
-    const size_t ntype = (size_t)nview * nbody;
-    HostInts host_types, host_ids, host_dims;
-    if (!host_types.copy(shape_type, ntype, st) || !host_ids.copy(grid_id, ntype, st) ||
-        (ngrid > 0 && !host_dims.copy(grid_dims, 3 * (size_t)ngrid, st)) || !host_sync(st))
-        return DSS_E_BADARG;
-    const int *types = host_types.p, *ids = host_ids.p, *dims = host_dims.p;
-    for (int g = 0; g < 3 * ngrid; ++g)
-        if (dims[g] < 2) return DSS_E_BADARG;
     bool any = false;
-    for (size_t i = 0; i < ntype; ++i) {
-        const bool level_set = types[i] == DSS_SHAPE_GRID || types[i] == DSS_SHAPE_IGR;
-        if (level_set && ids[i] >= ngrid) return DSS_E_BADARG;
-        if (level_set && ids[i] < 0) return DSS_E_UNSUPPORTED;      // a grid or neural body without a grid
-        if (!level_set && types[i] != DSS_SHAPE_BOX && types[i] != DSS_SHAPE_SPHERE && types[i] != DSS_SHAPE_CYLINDER &&
-            types[i] != DSS_SHAPE_BOX_ROUNDED)
-            return DSS_E_UNSUPPORTED;      // brick, bowl: as in dss_depth_render
-        if (level_set) any = true;
-    }
+    if (const int rc = judge_shapes((size_t)nview * nbody, shape_type, SHAPES_CONVEX, SHAPES_GRID_IGR, grid_id, ngrid, grid_dims, st, &any))
+        return rc;
     if (any)
-        hipLaunchKernelGGL(depth_render_grids_kernel, dim3(tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, tiles_x, tiles_per_view,
-                           pose, shape_type, prm, cam, fx, fy, cx, cy, W, H, znear, zfar, grid_id, grid_off, grid_dims, grid_data, blk_off,
-                           blk_min, depth, seg);
+        hipLaunchKernelGGL(depth_render_grids_kernel, dim3(L.tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, L.tiles_x,
+                           L.tiles_per_view, pose, shape_type, prm, cam, fx, fy, cx, cy, W, H, znear, zfar, grid_id, grid_off, grid_dims,
+                           grid_data, blk_off, blk_min, depth, seg);
     else      // no body is seen through a grid: the analytic renderer's own kernel, the same bits as dss_depth_render
-        hipLaunchKernelGGL(depth_render_kernel, dim3(tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, tiles_x, tiles_per_view, pose,
-                           shape_type, prm, cam, fx, fy, cx, cy, W, H, znear, zfar, depth, seg);
+        hipLaunchKernelGGL(depth_render_kernel, dim3(L.tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, L.tiles_x, L.tiles_per_view,
+                           pose, shape_type, prm, cam, fx, fy, cx, cy, W, H, znear, zfar, depth, seg);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }
 

@@ -263,4 +263,21 @@ template <bool GRIDS> __device__ __forceinline__ int dc_trace_body(const DcBody 
 
 inline bool dc_images_ok(int nview, int H, int W) { return nview > 0 && H > 0 && W > 0 && (long long)nview * H * W <= 0x7fffffffLL; }
 
+// The launch shape of the tiled camera kernels (a workgroup per DC_TILE x DC_TILE pixels of a view, grid.x = tiles_per_view * nview)
+// and whether the compiled limits hold it: nbody, the pixels' int indices, grid.x.  Host code.
+struct DcLaunch {
+    int tiles_x, tiles_per_view;
+    bool ok;
+};
+inline DcLaunch dc_launch_shape(int nview, int nbody, int W, int H)
+{
+    DcLaunch L = {0, 0, nbody <= DC_MAX_BODY && dc_images_ok(nview, H, W)};
+    if (L.ok) {      // (the pixels fit an int, so the tiles do)
+        L.tiles_x = (W - 1) / DC_TILE + 1;
+        L.tiles_per_view = L.tiles_x * ((H - 1) / DC_TILE + 1);
+        L.ok = (long long)L.tiles_per_view * nview <= 0x7fffffffLL;      // grid.x
+    }
+    return L;
+}
+
 }  // namespace

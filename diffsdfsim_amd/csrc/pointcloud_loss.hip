@@ -12,7 +12,7 @@
 // launch shape alone, so two calls on the same input return the same bits.
 // 24 B read per point against ~1 500 fp64 instructions (the dual-number SDF): VALU-bound, like dss_sdf_query.
 #include "../../include/diffsdfsim_hip.h"
-#include "pointcloud_args.h"
+#include "shape_args.h"
 #include "chunk_grid.h"
 #include "../../include/pointcloud_loss.h"
 #include "pointcloud_point.h"
@@ -125,7 +125,7 @@ int dss_pointcloud_loss(int nseg, int max_seg_len, const int *seg_off, const dou
     if (need > 0 && (!workspace || workspace_bytes < need)) return DSS_E_WORKSPACE;
     // the shape types decide the status (neural and grid bodies: not in this loss), so the host reads them before anything is enqueued
     hipStream_t st = (hipStream_t)stream;
-    if (const int rc = pc_judge_segments(nseg, shape_type, nullptr, 0, nullptr, st)) return rc;
+    if (const int rc = judge_shapes(nseg, shape_type, SHAPES_ANALYTIC, SHAPES_GRID, nullptr, 0, nullptr, st)) return rc;
     const int chunks = pc_chunks(max_seg_len);
     if (chunks > 0)
         hipLaunchKernelGGL(pointcloud_loss_kernel, dim3(chunks * nseg), dim3(CG_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,
@@ -147,7 +147,7 @@ int dss_pointcloud_loss_grids(int nseg, int max_seg_len, const int *seg_off, con
     if (need > 0 && (!workspace || workspace_bytes < need)) return DSS_E_WORKSPACE;
     // shape types, grid ids and the grids' dims decide the status: the host reads them before anything is enqueued
     hipStream_t st = (hipStream_t)stream;
-    if (const int rc = pc_judge_segments(nseg, shape_type, grid_id, ngrid, grid_dims, st)) return rc;
+    if (const int rc = judge_shapes(nseg, shape_type, SHAPES_ANALYTIC, SHAPES_GRID, grid_id, ngrid, grid_dims, st)) return rc;
     const int chunks = pc_chunks(max_seg_len);
     if (chunks > 0)
         hipLaunchKernelGGL(pointcloud_loss_grids_kernel, dim3(chunks * nseg), dim3(CG_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,

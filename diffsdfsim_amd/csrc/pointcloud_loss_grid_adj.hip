@@ -13,7 +13,7 @@
 // adds into one sample is the order of arrival: two calls agree to the rounding of an n-term sum, not in their bits.  Nothing is
 // merged before the adds.
 #include "../../include/diffsdfsim_hip.h"
-#include "pointcloud_args.h"
+#include "shape_args.h"
 #include "chunk_grid.h"
 #include "../../include/pointcloud_loss.h"
 #include "pointcloud_point.h"
@@ -71,7 +71,7 @@ extern "C" int dss_pointcloud_loss_grids_adjoint(int nseg, int max_seg_len, cons
     // shape types, grid ids and the grids' dims decide the status, as in dss_pointcloud_loss_grids: the host reads them first
     hipStream_t st = (hipStream_t)stream;
     bool any = false;
-    if (const int rc = pc_judge_segments(nseg, shape_type, grid_id, ngrid, grid_dims, st, &any)) return rc;
+    if (const int rc = judge_shapes(nseg, shape_type, SHAPES_ANALYTIC, SHAPES_GRID, grid_id, ngrid, grid_dims, st, &any)) return rc;
     const int chunks = pc_chunks(max_seg_len);
     if (!any || chunks == 0) return DSS_OK;      // no grid segment, or no point: nothing to add
     hipLaunchKernelGGL(pointcloud_grid_adjoint_kernel, dim3(chunks * nseg), dim3(CG_THREADS), 0, st, max_seg_len, chunks, seg_off, pts, pose,

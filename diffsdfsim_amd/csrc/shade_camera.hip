@@ -13,6 +13,7 @@
 #include <math.h>
 
 #include "depth_trace.h"
+#include "shape_args.h"
 #include "../../include/shade_camera.h"
 
 namespace {
@@ -193,30 +194,15 @@ extern "C" int dss_shade_render(int nview, int nbody, const double *pose, const 
     if (nlight < 0 || nlight > SH_MAX_LIGHT || (nlight > 0 && !light) || !(shadow_bias > 0.0)) return DSS_E_BADARG;
     if (ngrid > 0 && (!grid_id || !grid_off || !grid_dims || !grid_data || !blk_off || !blk_min)) return DSS_E_BADARG;
     if (!(fx != 0.0) || !(fy != 0.0) || !(zfar > 0.0)) return DSS_E_BADARG;
-    if (nbody > DC_MAX_BODY || !dc_images_ok(nview, H, W)) return DSS_E_UNSUPPORTED;
-    const int tiles_x = (W + DC_TILE - 1) / DC_TILE, tiles_per_view = tiles_x * ((H + DC_TILE - 1) / DC_TILE);
-    if ((long long)tiles_per_view * nview > 0x7fffffffLL) return DSS_E_UNSUPPORTED;      // grid.x
-    // shape types, grid ids and the grids' dims decide the status, so the host reads them before anything is enqueued
+    const DcLaunch L = dc_launch_shape(nview, nbody, W, H);
+    if (!L.ok) return DSS_E_UNSUPPORTED;
+    // Shape types, grid ids and the grids' dims decide the status, so the host reads them before anything is enqueued; without a
+    // table (ngrid = 0) grid_id is not read, and a level-set body has no grid.
     hipStream_t st = (hipStream_t)stream;
-    const size_t ntype = (size_t)nview * nbody;
-    HostInts host_types, host_ids, host_dims;
-    if (!host_types.copy(shape_type, ntype, st) ||
-        (ngrid > 0 && (!host_ids.copy(grid_id, ntype, st) || !host_dims.copy(grid_dims, 3 * (size_t)ngrid, st))) || !host_sync(st))
-        return DSS_E_BADARG;
-    const int *types = host_types.p, *ids = host_ids.p, *dims = host_dims.p;
-    for (int g = 0; g < 3 * ngrid; ++g)
-        if (dims[g] < 2) return DSS_E_BADARG;
     bool any = false;
-    for (size_t i = 0; i < ntype; ++i) {
-        const bool level_set = types[i] == DSS_SHAPE_GRID || types[i] == DSS_SHAPE_IGR;
-        const int id = (level_set && ids) ? ids[i] : -1;
-        if (level_set && id >= ngrid) return DSS_E_BADARG;
-        if (level_set && id < 0) return DSS_E_UNSUPPORTED;      // a grid or neural body without a grid
-        if (!level_set && types[i] != DSS_SHAPE_BOX && types[i] != DSS_SHAPE_SPHERE && types[i] != DSS_SHAPE_CYLINDER &&
-            types[i] != DSS_SHAPE_BOX_ROUNDED)
-            return DSS_E_UNSUPPORTED;      // brick, bowl: as in the depth camera
-        if (level_set) any = true;
-    }
+    if (const int rc = judge_shapes((size_t)nview * nbody, shape_type, SHAPES_CONVEX, SHAPES_GRID_IGR, ngrid > 0 ? grid_id : nullptr, ngrid,
+                                    grid_dims, st, &any))
+        return rc;
     ShArgs A;
     A.cam = cam; A.fx = fx; A.fy = fy; A.cx = cx; A.cy = cy; A.W = W; A.H = H; A.zfar = zfar;
     A.depth = depth; A.seg = seg; A.color = color; A.ambient = ambient;
@@ -224,10 +210,10 @@ extern "C" int dss_shade_render(int nview, int nbody, const double *pose, const 
     A.shadows = shadows != 0; A.bias = shadow_bias;
     A.normal = normal; A.shade = shade; A.rgb = rgb; A.flags = flags;
     if (any)
-        hipLaunchKernelGGL(shade_render_grids_kernel, dim3(tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, nlight, tiles_x, tiles_per_view,
-                           pose, shape_type, prm, light, grid_id, grid_off, grid_dims, grid_data, blk_off, blk_min, A);
+        hipLaunchKernelGGL(shade_render_grids_kernel, dim3(L.tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, nlight, L.tiles_x,
+                           L.tiles_per_view, pose, shape_type, prm, light, grid_id, grid_off, grid_dims, grid_data, blk_off, blk_min, A);
     else
-        hipLaunchKernelGGL(shade_render_kernel, dim3(tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, nlight, tiles_x, tiles_per_view,
-                           pose, shape_type, prm, light, A);
+        hipLaunchKernelGGL(shade_render_kernel, dim3(L.tiles_per_view * nview), dim3(DC_THREADS), 0, st, nbody, nlight, L.tiles_x,
+                           L.tiles_per_view, pose, shape_type, prm, light, A);
     return hipGetLastError() == hipSuccess ? DSS_OK : DSS_E_UNSUPPORTED;
 }

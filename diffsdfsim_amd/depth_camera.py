@@ -36,6 +36,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .grids import as_table, table_and_ids
 
 MAX_BODIES = 8
 
@@ -54,15 +55,62 @@ def _intrinsics(fx, fy, cx, cy):
     return fx, fy, cx, cy
 
 
-def render_depth(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640, 480), znear=0.1, zfar=100.0, grids=None, grid_id=None):
-    """-> (depth [nview,H,W] float64, seg [nview,H,W] int32) on the device of `pose`; size = (W, H).  See the module's text."""
-    _lib.require_device(pose, prm)
+def _scene(pose, shape_type, prm, nview=None):
+    """The validated scene -> (pose, prm, types: detached, contiguous, on the device of `pose`; nview, nbody).  nview: the views that
+    images passed beside the scene have."""
     if pose.dim() != 3 or pose.shape[2] != 7 or pose.dtype != torch.float64 or prm.dtype != torch.float64 or \
-            tuple(prm.shape) != (pose.shape[0], pose.shape[1], 4):
-        raise ValueError("pose [nview,nbody,7] and prm [nview,nbody,4] as float64, got %s and %s" % (tuple(pose.shape), tuple(prm.shape)))
+            tuple(prm.shape) != (pose.shape[0], pose.shape[1], 4) or (nview is not None and pose.shape[0] != nview):
+        raise ValueError("pose [nview,nbody,7] and prm [nview,nbody,4] as float64%s, got %s and %s" %
+                         ("" if nview is None else " for the %d views of depth" % nview, tuple(pose.shape), tuple(prm.shape)))
     nview, nbody = pose.shape[:2]
     if nview < 1 or not 1 <= nbody <= MAX_BODIES:
         raise ValueError("at least one view of 1 to %d bodies, got %d views of %d" % (MAX_BODIES, nview, nbody))
+    types = torch.as_tensor(shape_type).to(pose.device, torch.int32).reshape(nview, nbody).contiguous()
+    return pose.detach().contiguous(), prm.detach().contiguous(), types, nview, nbody
+
+
+def _image_pair(depth, seg):
+    """The validated images -> (depth, seg contiguous, nview, H, W)."""
+    if depth.dim() != 3 or depth.shape != seg.shape or depth.dtype != torch.float64 or seg.dtype != torch.int32:
+        raise ValueError("depth float64 and seg int32, both [nview,H,W], got %s %s and %s %s" %
+                         (tuple(depth.shape), depth.dtype, tuple(seg.shape), seg.dtype))
+    nview, H, W = depth.shape
+    if nview < 1 or H < 1 or W < 1 or nview * H * W > 2 ** 31 - 1:
+        raise ValueError("at least one pixel and nview * H * W < 2^31, got %s" % (tuple(depth.shape),))
+    return depth.contiguous(), seg.contiguous(), nview, H, W
+
+
+def _table(grids, grid_id, nview, nbody, dev):
+    """-> (the GridTable of `grids`, its checked ids [nview,nbody] on dev), or (None, None) without grids."""
+    return (None, None) if grids is None else table_and_ids(grids, grid_id, (nview, nbody), dev, "nview,nbody")
+
+
+def _grid_args(table, ids, block_min=True):
+    """The grid arguments of a camera entry: grid_id, ngrid, grid_off, grid_dims, grid_data and, for the entries that trace,
+    blk_off and blk_min; without a table ngrid = 0 and every pointer NULL."""
+    if table is None:
+        arrays = (None,) * (5 if block_min else 3)
+    else:
+        arrays = (table.off, table.dims, table.data.detach()) + ((table.blk_off, table.block_min()) if block_min else ())
+    return (_lib.ptr(ids), 0 if table is None else table.ngrid) + tuple(_lib.ptr(a) for a in arrays)
+
+
+def _view_chunks(pose, shape_type, grids, grid_id, per):
+    """What observe and render_color walk: types [nview,nbody] on the device, the table (made once: its block minima are shared by
+    the chunks) and, per chunk of `per` views, (its slice, its grid ids or None)."""
+    nview = pose.shape[0]
+    types = torch.as_tensor(shape_type).to(pose.device, torch.int32).reshape(nview, -1)
+    if grids is not None:
+        grids = as_table(grids, pose.device)
+        grid_id = torch.as_tensor(grid_id).reshape(nview, -1)
+    slices = [slice(v0, v0 + per) for v0 in range(0, nview, per)]
+    return types, grids, [(sl, None if grids is None else grid_id[sl]) for sl in slices]
+
+
+def render_depth(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640, 480), znear=0.1, zfar=100.0, grids=None, grid_id=None):
+    """-> (depth [nview,H,W] float64, seg [nview,H,W] int32) on the device of `pose`; size = (W, H).  See the module's text."""
+    _lib.require_device(pose, prm)
+    pose, prm, types, nview, nbody = _scene(pose, shape_type, prm)
     W, H = int(size[0]), int(size[1])
     if W < 1 or H < 1 or nview * W * H > 2 ** 31 - 1:
         raise ValueError("size = (W, H), positive, nview * W * H < 2^31 (render in chunks of views: observe), got %r for %d views" % (size, nview))
@@ -70,19 +118,13 @@ def render_depth(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640, 480
         raise ValueError("0 <= znear < zfar, got %r, %r" % (znear, zfar))
     fx, fy, cx, cy = _intrinsics(fx, fy, cx, cy)
     dev = pose.device
-    types = torch.as_tensor(shape_type).to(dev, torch.int32).reshape(nview, nbody).contiguous()
     depth = torch.zeros(nview, H, W, dtype=torch.float64, device=dev)
     seg = torch.full((nview, H, W), -1, dtype=torch.int32, device=dev)
-    cam, pose, prm = _camera(cam_pose, dev), pose.detach().contiguous(), prm.detach().contiguous()
-    if grids is not None:
-        from .grids import as_table
-        T = as_table(grids, dev)
-        if grid_id is None:
-            raise ValueError("grids= needs grid_id [nview,nbody] (-1: the body has no grid)")
-        ids = T.ids(grid_id, (nview, nbody), dev)
+    cam = _camera(cam_pose, dev)
+    T, ids = _table(grids, grid_id, nview, nbody, dev)
+    if T is not None:
         rc = _lib.lib().dss_depth_render_grids(nview, nbody, _lib.ptr(pose), _lib.ptr(types), _lib.ptr(prm), _lib.ptr(cam), fx, fy, cx, cy, W, H,
-                                               float(znear), float(zfar), _lib.ptr(ids), T.ngrid, _lib.ptr(T.off), _lib.ptr(T.dims),
-                                               _lib.ptr(T.data), _lib.ptr(T.blk_off), _lib.ptr(T.block_min()), _lib.ptr(depth), _lib.ptr(seg),
+                                               float(znear), float(zfar), *_grid_args(T, ids), _lib.ptr(depth), _lib.ptr(seg),
                                                _lib.stream_ptr(dev))
         if rc == -3:
             raise _lib.HipLibraryError("dss_depth_render_grids: the renderer takes shape types 0-3 and, with a grid_id >= 0, grid and "
@@ -105,15 +147,9 @@ def observed_points(depth, seg, body, cam_pose, fx, fy, cx, cy):
     dropped, back-projected; row-major pixel order per view.  -> (pts [N,3] float64 on the device, seg_off [nview+1] int64 numpy:
     view v owns pts[seg_off[v]:seg_off[v+1]])."""
     _lib.require_device(depth, seg)
-    if depth.dim() != 3 or depth.shape != seg.shape or depth.dtype != torch.float64 or seg.dtype != torch.int32:
-        raise ValueError("depth float64 and seg int32, both [nview,H,W], got %s %s and %s %s" %
-                         (tuple(depth.shape), depth.dtype, tuple(seg.shape), seg.dtype))
-    nview, H, W = depth.shape
-    if nview < 1 or H < 1 or W < 1 or nview * H * W > 2 ** 31 - 1:
-        raise ValueError("at least one pixel and nview * H * W < 2^31, got %s" % (tuple(depth.shape),))
+    depth, seg, nview, H, W = _image_pair(depth, seg)
     fx, fy, cx, cy = _intrinsics(fx, fy, cx, cy)
     dev = depth.device
-    depth, seg = depth.contiguous(), seg.contiguous()
     count, emit = _lib.lib().dss_depth_points_count, _lib.lib().dss_depth_points_emit
     rows = torch.zeros(nview * H, dtype=torch.int32, device=dev)
     _lib.check(count(nview, H, W, int(body), _lib.ptr(depth), _lib.ptr(seg), _lib.ptr(rows), _lib.stream_ptr(dev)), "dss_depth_points_count")
@@ -140,19 +176,12 @@ def observe(pose, shape_type, prm, body, cam_pose, fx, fy, cx, cy, size=(640, 48
     does, depth += randn * noise * depth^2 (a pixel of depth 0 stays 0), from a generator seeded with `seed` on the device.
     grids, grid_id [nview,nbody]: as in render_depth.
     -> (pts [N,3], seg_off [nview+1]) as observed_points returns them."""
-    nview = pose.shape[0]
-    per = views_per_chunk(size, max_bytes)
     gen = torch.Generator(device=pose.device)
     gen.manual_seed(int(seed))
-    types = torch.as_tensor(shape_type).to(pose.device, torch.int32).reshape(nview, -1)
+    types, grids, chunks = _view_chunks(pose, shape_type, grids, grid_id, views_per_chunk(size, max_bytes))
     pts, off = [], [np.zeros(1, np.int64)]
-    if grids is not None:
-        from .grids import as_table
-        grids = as_table(grids, pose.device)      # (once: its block minima are shared by the chunks)
-        grid_id = torch.as_tensor(grid_id).reshape(nview, -1)
-    for v0 in range(0, nview, per):
-        depth, seg = render_depth(pose[v0:v0 + per], types[v0:v0 + per], prm[v0:v0 + per], cam_pose, fx, fy, cx, cy, size, znear, zfar,
-                                  grids, None if grids is None else grid_id[v0:v0 + per])
+    for sl, gid in chunks:
+        depth, seg = render_depth(pose[sl], types[sl], prm[sl], cam_pose, fx, fy, cx, cy, size, znear, zfar, grids, gid)
         if noise > 0:
             depth += torch.randn(depth.shape, dtype=depth.dtype, device=depth.device, generator=gen) * noise * depth ** 2
         p, o = observed_points(depth, seg, body, cam_pose, fx, fy, cx, cy)
@@ -182,42 +211,23 @@ def shade(depth, seg, pose, shape_type, prm, cam_pose, fx, fy, cx, cy, colors, l
     min(1, ambient + sum_k I_k V_k max(0, n . l_k)), flags [nview,H,W] uint8: bit 0 a shadow ray used up its iterations, bit 1
     the field's gradient vanished and the normal faces the camera) on the device."""
     _lib.require_device(depth, seg, pose, prm)
-    if depth.dim() != 3 or depth.shape != seg.shape or depth.dtype != torch.float64 or seg.dtype != torch.int32:
-        raise ValueError("depth float64 and seg int32, both [nview,H,W], got %s %s and %s %s" %
-                         (tuple(depth.shape), depth.dtype, tuple(seg.shape), seg.dtype))
-    nview, H, W = depth.shape
-    if pose.dim() != 3 or tuple(pose.shape) != (nview, pose.shape[1], 7) or pose.dtype != torch.float64 or prm.dtype != torch.float64 or \
-            tuple(prm.shape) != (nview, pose.shape[1], 4):
-        raise ValueError("pose [nview,nbody,7] and prm [nview,nbody,4] as float64 for the %d views of depth, got %s and %s" %
-                         (nview, tuple(pose.shape), tuple(prm.shape)))
-    nbody = pose.shape[1]
-    if nview < 1 or H < 1 or W < 1 or nview * H * W > 2 ** 31 - 1 or not 1 <= nbody <= MAX_BODIES:
-        raise ValueError("at least one pixel, nview * H * W < 2^31 and 1 to %d bodies, got %s with %d" % (MAX_BODIES, tuple(depth.shape), nbody))
+    depth, seg, nview, H, W = _image_pair(depth, seg)
+    pose, prm, types, nview, nbody = _scene(pose, shape_type, prm, nview)
     if not shadow_bias > 0.0 or not zfar > 0.0:
         raise ValueError("shadow_bias > 0 and zfar > 0, got %r, %r" % (shadow_bias, zfar))
     fx, fy, cx, cy = _intrinsics(fx, fy, cx, cy)
     dev = depth.device
     fn = _lib.lib().dss_shade_render
-    types = torch.as_tensor(shape_type).to(dev, torch.int32).reshape(nview, nbody).contiguous()
     col = torch.as_tensor(colors, dtype=torch.float64).to(dev)
     col = (col.expand(nview, nbody, 3) if col.dim() == 2 else col.reshape(nview, nbody, 3)).contiguous()
     lt, nlight = _lights(lights, dev)
     bg = (ctypes.c_double * 3)(*[float(b) for b in background])
-    cam, pose, prm = _camera(cam_pose, dev), pose.detach().contiguous(), prm.detach().contiguous()
-    depth, seg = depth.contiguous(), seg.contiguous()
+    cam = _camera(cam_pose, dev)
     rgb = torch.zeros(nview, H, W, 3, dtype=torch.uint8, device=dev)
     normal = torch.zeros(nview, H, W, 3, dtype=torch.float64, device=dev)
     shd = torch.zeros(nview, H, W, dtype=torch.float64, device=dev)
     flags = torch.zeros(nview, H, W, dtype=torch.uint8, device=dev)
-    if grids is not None:
-        from .grids import as_table
-        T = as_table(grids, dev)
-        if grid_id is None:
-            raise ValueError("grids= needs grid_id [nview,nbody] (-1: the body has no grid)")
-        ids = T.ids(grid_id, (nview, nbody), dev)
-        gargs = (_lib.ptr(ids), T.ngrid, _lib.ptr(T.off), _lib.ptr(T.dims), _lib.ptr(T.data), _lib.ptr(T.blk_off), _lib.ptr(T.block_min()))
-    else:
-        gargs = (None, 0, None, None, None, None, None)
+    gargs = _grid_args(*_table(grids, grid_id, nview, nbody, dev))
     rc = fn(nview, nbody, _lib.ptr(pose), _lib.ptr(types), _lib.ptr(prm), _lib.ptr(cam), fx, fy, cx, cy, W, H, float(zfar), *gargs,
             _lib.ptr(depth), _lib.ptr(seg), _lib.ptr(col), nlight, None if lt is None else _lib.ptr(lt), float(ambient),
             ctypes.cast(bg, ctypes.c_void_p), int(bool(shadows)), float(shadow_bias), _lib.ptr(normal), _lib.ptr(shd), _lib.ptr(rgb),
@@ -238,19 +248,12 @@ def render_color(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, colors, lights
     """render_depth, then shade, over all views, at most `max_bytes` of images at a time (views_per_chunk with the 36 further
     bytes per pixel that shade writes).  -> (rgb [nview,H,W,3] uint8, depth [nview,H,W] float64, seg [nview,H,W] int32)."""
     nview = pose.shape[0]
-    per = views_per_chunk(size, max_bytes, _COLOR_BYTES)
-    types = torch.as_tensor(shape_type).to(pose.device, torch.int32).reshape(nview, -1)
+    types, grids, chunks = _view_chunks(pose, shape_type, grids, grid_id, views_per_chunk(size, max_bytes, _COLOR_BYTES))
     col = torch.as_tensor(colors, dtype=torch.float64)
     if col.dim() == 2:
         col = col.expand(nview, *col.shape)
-    if grids is not None:
-        from .grids import as_table
-        grids = as_table(grids, pose.device)      # (once: its block minima are shared by the chunks)
-        grid_id = torch.as_tensor(grid_id).reshape(nview, -1)
     out = []
-    for v0 in range(0, nview, per):
-        sl = slice(v0, v0 + per)
-        gid = None if grids is None else grid_id[sl]
+    for sl, gid in chunks:
         depth, seg = render_depth(pose[sl], types[sl], prm[sl], cam_pose, fx, fy, cx, cy, size, znear, zfar, grids, gid)
         rgb = shade(depth, seg, pose[sl], types[sl], prm[sl], cam_pose, fx, fy, cx, cy, col[sl], lights, ambient, background, shadows,
                     shadow_bias, zfar, grids, gid)[0]
@@ -285,14 +288,14 @@ class _RenderDepth(torch.autograd.Function):
     def forward(ctx, pose, prm, grid_data, types, cam, intr, size, znear, zfar, grids, ids, min_cos, dropped_out):
         pose_c, prm_c = pose.detach().contiguous(), prm.detach().contiguous()
         depth, seg = render_depth(pose_c, types, prm_c, cam, *intr, size, znear, zfar, grids, ids)
-        ctx.save_for_backward(pose_c, prm_c, types, cam, depth, seg, *(() if grids is None else (ids, grids.off, grids.dims, grids.data.detach())))
-        ctx.intr, ctx.size, ctx.min_cos, ctx.ngrid, ctx.dropped_out = intr, size, float(min_cos), 0 if grids is None else grids.ngrid, dropped_out
+        ctx.save_for_backward(pose_c, prm_c, types, cam, depth, seg, *(() if grids is None else (ids,)))
+        ctx.intr, ctx.size, ctx.min_cos, ctx.table, ctx.dropped_out = intr, size, float(min_cos), grids, dropped_out
         ctx.mark_non_differentiable(seg)
         return depth, seg
 
     @staticmethod
     def backward(ctx, g_depth, _g_seg):
-        pose, prm, types, cam, depth, seg, *gt = ctx.saved_tensors
+        pose, prm, types, cam, depth, seg, *ids = ctx.saved_tensors
         fn = getattr(_lib.lib(), "dss_depth_adjoint", None)
         if fn is None:
             raise _lib.HipLibraryError("the library does not export dss_depth_adjoint: rebuild it (python __graft_entry__.py build)")
@@ -305,16 +308,10 @@ class _RenderDepth(torch.autograd.Function):
         dropped = torch.zeros(nview, nbody, dtype=torch.int32, device=dev)
         nbytes = _lib.lib().dss_depth_adjoint_workspace_bytes(nview, nbody, W, H)
         ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
-        g_grid = None
-        if gt:
-            ids, off, dims, data = gt
-            if ctx.needs_input_grad[2]:
-                g_grid = torch.zeros_like(data)
-            gargs = (_lib.ptr(ids), ctx.ngrid, _lib.ptr(off), _lib.ptr(dims), _lib.ptr(data))
-        else:
-            gargs = (None, 0, None, None, None)
+        g_grid = torch.zeros_like(ctx.table.data) if ids and ctx.needs_input_grad[2] else None
+        gargs = _grid_args(ctx.table, *ids or (None,), block_min=False)
         rc = fn(nview, nbody, _lib.ptr(pose), _lib.ptr(types), _lib.ptr(prm), _lib.ptr(cam), *ctx.intr, W, H, _lib.ptr(depth), _lib.ptr(seg),
-                _lib.ptr(g_depth), ctx.min_cos, *gargs, _lib.ptr(g_pose), _lib.ptr(g3), None if g_grid is None else _lib.ptr(g_grid),
+                _lib.ptr(g_depth), ctx.min_cos, *gargs, _lib.ptr(g_pose), _lib.ptr(g3), _lib.ptr(g_grid),
                 _lib.ptr(dropped), _lib.ptr(ws), nbytes, _lib.stream_ptr(dev))
         _lib.check(rc, "dss_depth_adjoint")
         g_prm[..., :3] = g3
@@ -340,16 +337,9 @@ def render_depth_diff(pose, shape_type, prm, cam_pose, fx, fy, cx, cy, size=(640
     if not 0.0 <= float(min_cos) <= 1.0:
         raise ValueError("min_cos in [0, 1], got %r" % (min_cos,))
     dev = pose.device
-    nview, nbody = pose.shape[:2]
+    _, _, types, nview, nbody = _scene(pose, shape_type, prm)
     W, H = int(size[0]), int(size[1])
-    types = torch.as_tensor(shape_type).to(dev, torch.int32).reshape(nview, nbody).contiguous()
-    table, ids = None, None
-    if grids is not None:
-        from .grids import as_table
-        table = as_table(grids, dev)
-        if grid_id is None:
-            raise ValueError("grids= needs grid_id [nview,nbody] (-1: the body has no grid)")
-        ids = table.ids(grid_id, (nview, nbody), dev)
+    table, ids = _table(grids, grid_id, nview, nbody, dev)
     data = table.data if table is not None and table.data.requires_grad else None
     dropped = torch.zeros(nview, nbody, dtype=torch.int32, device=dev) if return_dropped else None
     depth, seg = _RenderDepth.apply(pose, prm, data, types, _camera(cam_pose, dev), _intrinsics(fx, fy, cx, cy), (W, H), float(znear), float(zfar),

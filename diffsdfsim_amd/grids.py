@@ -80,3 +80,12 @@ class GridTable:
 
 def as_table(grids, device=None):
     return grids if isinstance(grids, GridTable) else GridTable(grids, device)
+
+
+def table_and_ids(grids, grid_id, shape, device, axes):
+    """What a call with grids= passes on -> (as_table(grids), its checked ids of `shape` on the device).  axes: the shape in words
+    for the error ("nview,nbody", "nseg")."""
+    if grid_id is None:
+        raise ValueError("grids= needs grid_id [%s] (-1: no grid there)" % axes)
+    T = as_table(grids, device)
+    return T, T.ids(grid_id, shape, device)

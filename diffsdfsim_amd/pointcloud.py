@@ -193,11 +193,9 @@ def _match_with_neural(pts, off, pose, types, prm, grids, grid_id, igr, latent, 
         do = ids_o.to(dev)
         T = gid = None
         if grids is not None:
-            from .grids import as_table
-            if grid_id is None:
-                raise ValueError("grids= needs grid_id [nseg] (-1: the segment's body has no grid)")
-            T = as_table(grids, dev)
-            gid = T.ids(grid_id, (nseg,), dev)[do].contiguous()
+            from .grids import table_and_ids
+            T, gid = table_and_ids(grids, grid_id, (nseg,), dev, "nseg")
+            gid = gid[do].contiguous()
         s, n = _match_grids(p_o, off_o.to(dev, torch.int32), max_o, pose[do], types[do].contiguous(), prm[do], T, gid)
         loss, count = loss.index_copy(0, do, s), count.index_copy(0, do, n)
     return loss, count.detach()
@@ -222,8 +220,5 @@ def match_pointcloud(pts, seg_off, pose, shape_type, prm, grids=None, grid_id=No
         return _match_with_neural(pts, off, pose, types, prm, grids, grid_id, igr, latent, latent_id, neural)
     if grids is None:
         return _MatchPointcloud.apply(pts, off_d, max_len, pose, types, prm, None, None)
-    from .grids import as_table
-    if grid_id is None:
-        raise ValueError("grids= needs grid_id [nseg] (-1: the segment's body has no grid)")
-    T = as_table(grids, dev)
-    return _match_grids(pts, off_d, max_len, pose, types, prm, T, T.ids(grid_id, (nseg,), dev))
+    from .grids import table_and_ids
+    return _match_grids(pts, off_d, max_len, pose, types, prm, *table_and_ids(grids, grid_id, (nseg,), dev, "nseg"))

@@ -32,7 +32,8 @@ extern "C" {
  *   shade = min(1, ambient + sum_k I_k V_k max(0, c_k)),  rgb_c = (unsigned char) floor(255 color_c shade + 0.5).
  * Outputs: normal [nview][H][W][3] and shade [nview][H][W] (double), rgb [nview][H][W][3] and flags [nview][H][W] (unsigned char).
  * No atomics: every output is a function of the inputs alone, two calls return the same bits.
- * DSS_E_BADARG: a null pointer, a non-positive size, nlight outside 0..4, shadow_bias <= 0, ngrid < 0, a grid id >= ngrid.
+ * DSS_E_BADARG: a null pointer, a non-positive size, nlight outside 0..4, shadow_bias <= 0, ngrid < 0, a grid id >= ngrid,
+ * a grid dim < 2.
  * DSS_E_UNSUPPORTED, every output untouched: nbody > 8, a brick or a bowl, a grid or neural body without a grid, images with
  * more than 2^31 - 1 pixels.  As in the depth camera the host reads shape_type (and grid_id, grid_dims) and waits for the
  * stream before it enqueues. */

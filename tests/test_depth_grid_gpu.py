@@ -74,7 +74,7 @@ def test_refused_inputs_raise_and_leave_the_outputs_alone(views, kind, gid):
                                            _lib.ptr(i), T.ngrid, _lib.ptr(T.off), _lib.ptr(T.dims), _lib.ptr(T.data), _lib.ptr(T.blk_off),
                                            _lib.ptr(T.block_min()), _lib.ptr(depth), _lib.ptr(seg), _lib.stream_ptr(torch.device(DEV)))
     torch.cuda.synchronize()
-    assert rc != 0 and bool((depth == -7.0).all()) and bool((seg == -7).all())
+    assert rc == -3 and bool((depth == -7.0).all()) and bool((seg == -7).all())
 
 
 def test_block_minima_equal_numpy(views):

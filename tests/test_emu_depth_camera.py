@@ -96,7 +96,7 @@ def test_unsupported_types_give_a_status_and_leave_the_outputs_alone(kind):
     pose, types, prm = ref.bounce_views()
     types = types[:2].copy(); types[1, 2] = kind
     rc, depth, seg = render(pose[:2], types, prm[:2], ref.experiment_camera(), fill=-7, **ref.SMALL)
-    assert rc != 0 and np.all(depth == -7.0) and np.all(seg == -7)
+    assert rc == -3 and np.all(depth == -7.0) and np.all(seg == -7)      # DSS_E_UNSUPPORTED
 
 
 def test_points_of_the_reference_golden():

@@ -97,7 +97,7 @@ def test_refused_inputs_give_a_status_and_leave_the_outputs_alone(kind, gid):
     types, ids = types.copy(), ids.copy()
     types[1, 3], ids[1, 3] = kind, gid
     rc, depth, seg = render(pose, types, prm, grids, ids, ref.experiment_camera(), fill=-7, **ref.SMALL)
-    assert rc != 0 and np.all(depth == -7.0) and np.all(seg == -7)
+    assert rc == -3 and np.all(depth == -7.0) and np.all(seg == -7)      # DSS_E_UNSUPPORTED
 
 
 def test_block_minima_equal_numpy():
